@@ -3,12 +3,20 @@
 logistic regression, d = 10^6, bf16 shards, one process per MI355X over RCCL.
 
 Driver contract:
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (for N > 1 the driver launches this under torch.distributed.run, one rank per
 GPU; RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* come from the env). W untimed warmup
 AGD iterations, then EXACTLY K timed iterations bracketed by a barrier +
 torch.cuda.synchronize() on both sides; elapsed is the MAX over ranks; rank 0
 prints ONE JSON line.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, write the outputs if --dump-outputs is given, print the line.
+--full adds the second half of the metric: an untimed convergence run that
+estimates L* and reports iters-to-eps (config.iters_to_eps / loss_star).
+--dump-outputs DIR writes what the timed run returned to its caller
+(DIR/weights.npy, DIR/loss_history.npy); the inputs are seeded, so two builds
+can be compared output for output.
 
 Metric: examples/sec — loss/gradient evaluations x rows per second,
 aggregated over all ranks. Each AGD iteration performs 2 evaluations (at y,
@@ -28,6 +36,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -111,6 +120,28 @@ def sync(device: torch.device) -> None:
         torch.cuda.synchronize(device)
 
 
+DUMP_BUDGET_BYTES = 64 * 2**20  # --dump-outputs writes at most this much
+
+
+def dump_outputs(out_dir: str, weights: torch.Tensor, hist) -> None:
+    """Write what run() returned for the timed window: the weight vector
+    (float32, or float64 when the solve ran in float64) and the loss history
+    (float64). A weight vector over the budget is written as a fixed, seeded
+    sample, with the sampled indices alongside."""
+    os.makedirs(out_dir, exist_ok=True)
+    h = np.asarray(hist, dtype=np.float64)
+    w = weights.detach().to("cpu")
+    w = w.numpy().astype(np.float64 if w.dtype == torch.float64 else np.float32)
+    budget = DUMP_BUDGET_BYTES - h.nbytes - 4096  # .npy headers
+    if w.nbytes > budget:
+        k = budget // (w.itemsize + 8)  # value + int64 index per sample
+        idx = np.sort(np.random.RandomState(0).choice(w.size, size=k, replace=False))
+        np.save(os.path.join(out_dir, "weights_sample_index.npy"), idx.astype(np.float64))
+        w = w[idx]
+    np.save(os.path.join(out_dir, "weights.npy"), w)
+    np.save(os.path.join(out_dir, "loss_history.npy"), h)
+
+
 def main() -> int:
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1)
@@ -150,8 +181,16 @@ def main() -> int:
     p.add_argument("--eps", type=float, default=1e-3,
                    help="iters-to-eps tolerance: iterations to loss <= (1+eps)*L*")
     p.add_argument("--eps-iters", type=int, default=-1,
-                   help="extra (untimed) iterations after the timed window used "
-                        "to estimate L* for iters-to-eps; -1 = auto, 0 = skip")
+                   help="with --full: extra (untimed) iterations past the timed "
+                        "window used to estimate L* for iters-to-eps; "
+                        "-1 = auto, 0 = skip")
+    p.add_argument("--full", action="store_true",
+                   help="also run the untimed convergence run behind "
+                        "iters-to-eps (off by default: a plain run only "
+                        "times its steps)")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="write the timed run's outputs (weights, loss "
+                        "history) as DIR/<name>.npy")
     p.add_argument("--streamed", action="store_true",
                    help="features in pinned host memory, double-buffered H2D "
                         "streaming (PCIe-bound capacity mode)")
@@ -261,18 +300,16 @@ def main() -> int:
 
     state = {"t0": 0.0, "t1": 0.0, "e0": 0, "e1": 0, "p0": 0, "p1": 0, "timed_iters": 0}
     total_iters = args.warmup + args.steps
-    # Convergence tail AFTER the timed window: extra untimed iterations that
-    # drive the trajectory near its optimum so L* (= min over the whole
-    # history) is converged and iters-to-eps is well-defined. Auto: enough to
-    # converge the bench configs, capped so the tail stays a few seconds.
-    eps_iters = args.eps_iters
+    # Convergence run AFTER the timed one (--full only): an untimed run past
+    # the timed window's length that drives the trajectory near its optimum
+    # so L* (= min over the whole history) is converged and iters-to-eps is
+    # well-defined. Auto: enough to converge the bench configs, capped so it
+    # stays a few seconds.
+    eps_iters = args.eps_iters if args.full else 0
     if eps_iters < 0:
         # 300 total on GPU: converges every bench config for a stable L*
-        # AND keeps the process busy for several seconds so the driver's
-        # SMI sampling sees real utilization
         eps_iters = 300 if device.type == "cuda" else 60
         eps_iters = max(0, eps_iters - total_iters)  # long runs converge alone
-    run_iters = total_iters + eps_iters
 
     def hook(n_iter: int):
         if n_iter == args.warmup:
@@ -282,14 +319,12 @@ def main() -> int:
             state["e0"] = gradient.n_evals
             state["p0"] = gradient.n_passes
         if n_iter == total_iters:
-            # close the timing window, then keep iterating (untimed) for L*
             comm.barrier()
             sync(device)
             state["t1"] = time.perf_counter()
             state["e1"] = gradient.n_evals
             state["p1"] = gradient.n_passes
             state["timed_iters"] = n_iter - args.warmup
-        if n_iter == run_iters:
             return "stop"
         return None
 
@@ -301,7 +336,7 @@ def main() -> int:
     weights, hist = run(
         shard, gradient, updater,
         0.0,                      # convergence_tol: never stop early in a bench
-        run_iters, args.reg, w0,
+        total_iters, args.reg, w0,
         1.0, math.inf, 0.5, 0.9, True,
         loss_history_mode="backtrack",
         comm=comm,
@@ -317,6 +352,23 @@ def main() -> int:
         state["e1"] = gradient.n_evals
         state["p1"] = gradient.n_passes
         state["timed_iters"] = max(len(hist) - args.warmup, 1)
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, weights, hist)
+
+    if eps_iters > 0:
+        # the same trajectory from w0 (seeded inputs, replicated control
+        # flow), carried eps_iters past the timed window; its history
+        # replaces the timed run's for L*, iters-to-eps and loss_final
+        _w_tail, hist = run(
+            shard, gradient, updater,
+            0.0, total_iters + eps_iters, args.reg, w0,
+            1.0, math.inf, 0.5, 0.9, True,
+            loss_history_mode="backtrack",
+            comm=comm,
+            solver=args.solver,
+            gram_op=gram_op,
+        )
 
     elapsed_local = state["t1"] - state["t0"]
     evals = state["e1"] - state["e0"]
@@ -350,7 +402,7 @@ def main() -> int:
         vs_baseline = value / (3.23e6 * world)
 
     # iters-to-eps: first iteration with loss <= (1+eps)*L*, L* = min over
-    # the full (timed + convergence-tail) history — the single definition
+    # the convergence run's history (--full) — the single definition
     # shared with benchmarks/iters_to_eps.py (utils.metrics.iters_to_eps).
     iters_to_eps = _iters_to_eps(hist, args.eps) if eps_iters > 0 or len(hist) >= 60 else None
 

@@ -21,7 +21,7 @@ run_cfg() {
 }
 
 E="--eps-iters 0"
-run_cfg headline_d1e6            --steps 20 --warmup 5            # full metric incl. iters-to-eps tail
+run_cfg headline_d1e6            --steps 20 --warmup 5 --full     # full metric incl. the iters-to-eps convergence run
 run_cfg csr_uniform_d1e7         --csr --rows 1000000 --dim 10000000 --steps 20 --warmup 3 $E
 run_cfg csr_zipf_d1e7            --csr --rows 1000000 --dim 10000000 --steps 20 --warmup 3 --csr-dist zipf $E
 run_cfg gram_headline            --solver gram --steps 100 --warmup 10 $E

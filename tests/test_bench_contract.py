@@ -21,7 +21,7 @@ def _run_bench(*extra):
 
 
 def test_bench_json_contract():
-    d = _run_bench()
+    d = _run_bench("--full")
     # the driver-mandated fields, with the mandated types/semantics
     assert d["metric"].startswith("examples/sec + iters-to-")
     assert isinstance(d["value"], float) and d["value"] > 0
@@ -41,12 +41,38 @@ def test_bench_json_contract():
                 "iters_to_eps", "eps", "loss_star", "shard_gb"):
         assert key in c, key
     assert c["parallelism"] == "dp1"
-    # the metric's second half must be non-null and meaningful by default
+    # the metric's second half must be non-null and meaningful under --full
+    assert c["eps_iters_tail"] > 0
     assert isinstance(c["iters_to_eps"], int) and c["iters_to_eps"] >= 1
     assert c["loss_star"] is not None
     # eval-examples definition: value = rows * evals/step * steps / elapsed
     ratio = d["value"] / d["rows_per_sec"]
     assert abs(ratio - c["evals_per_step"]) < 1e-6
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run times exactly --steps steps and skips the convergence
+    run; --dump-outputs writes what the timed run returned, identically
+    from run to run."""
+    import numpy as np
+
+    a, b = str(tmp_path / "a"), str(tmp_path / "b")
+    d = _run_bench("--dump-outputs", a)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    c = d["config"]
+    assert c["eps_iters_tail"] == 0 and c["iters_to_eps"] is None
+    _run_bench("--dump-outputs", b)
+    assert sorted(os.listdir(a)) == ["loss_history.npy", "weights.npy"]
+    w, h = (np.load(os.path.join(a, f"{n}.npy"))
+            for n in ("weights", "loss_history"))
+    assert w.dtype in (np.float32, np.float64) and w.shape == (c["d"],)
+    assert np.isfinite(w).all() and np.abs(w).max() > 0
+    # the history of the whole timed run: warmup + steps iterations
+    assert h.dtype == np.float64 and h.shape == (4,)
+    assert h[-1] == c["loss_final"]
+    for n in ("weights", "loss_history"):
+        assert np.array_equal(np.load(os.path.join(a, f"{n}.npy")),
+                              np.load(os.path.join(b, f"{n}.npy")))
 
 
 def test_bench_gram_contract():
