@@ -45,6 +45,7 @@ from .gram import GramOperator, run_gram
 from .parallel.comm import Communicator
 from . import evaluation
 from .streaming import HostStreamedDenseShard
+from .stats import ColumnSummary, StandardScaler, column_stats
 
 __version__ = "0.2.0"
 
@@ -87,4 +88,7 @@ __all__ = [
     "Communicator",
     "GramOperator",
     "run_gram",
+    "ColumnSummary",
+    "StandardScaler",
+    "column_stats",
 ]

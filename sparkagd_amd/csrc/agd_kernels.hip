@@ -1029,6 +1029,351 @@ __global__ __launch_bounds__(BLOCK) void k_csr_grad(
 }
 
 // ---------------------------------------------------------------------------
+// Column statistics + feature standardisation (preprocessing, not per-step).
+//
+// MLlib's Statistics.colStats / StandardScaler(withStd, !withMean) analog:
+// one streaming pass over the shard yields, per column, sum and sum of
+// squares (f64), min / max and the count of non-zero entries; a second family
+// of kernels multiplies every column by a per-column factor in place.
+// All of it is deterministic (no atomics, fixed reduction orders).
+// ---------------------------------------------------------------------------
+
+// Element type the statistics are read in: f32 for bf16/fp8/f32 shards (the
+// decode is exact), f64 for f64 shards.
+template <typename TA> struct StatVal { using type = float; };
+template <> struct StatVal<double> { using type = double; };
+
+// Dense column moments, same decomposition as k_dense_grad: grid over
+// (row-block x column-slab), W adjacent columns per lane from one 16-B
+// non-temporal load per row, private partial slabs written once. Both sums
+// accumulate in f64 from the first element (d = (double)v; sum += d;
+// sumsq = fma(d, d, sumsq)): an f32 running sum would already be off by
+// ~6e-8 relative per add, far outside the 1e-9 accuracy contract, and the
+// f64 square also covers f32 shards, whose squares are not exact in f32.
+template <typename TA, int W, bool NT>
+__global__ __launch_bounds__(BLOCK) void k_dense_colstats(
+    const TA* __restrict__ A, ll n, ll d, ll n_rb, double* __restrict__ psum,
+    double* __restrict__ psumsq, float* __restrict__ pmin,
+    float* __restrict__ pmax, int* __restrict__ pnnz) {
+  using TV = typename StatVal<TA>::type;
+  const ll cols_per_block = (ll)BLOCK * W;
+  const ll n_cs = (d + cols_per_block - 1) / cols_per_block;
+  for (ll b = blockIdx.x; b < n_rb * n_cs; b += gridDim.x) {
+    const ll rb = b / n_cs;
+    const ll cs = b - rb * n_cs;
+    const ll r_lo = rb * n / n_rb;
+    const ll r_hi = (rb + 1) * n / n_rb;
+    const ll c0 = cs * cols_per_block + (ll)threadIdx.x * W;
+    double s[W], q[W];
+    TV lo[W], hi[W];
+    int nz[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      s[k] = 0.0;
+      q[k] = 0.0;
+      lo[k] = (TV)INFINITY;
+      hi[k] = -(TV)INFINITY;
+      nz[k] = 0;
+    }
+    const bool full = (c0 + W <= d);
+    if (full) {
+      const TA* __restrict__ p = A + r_lo * d + c0;
+#pragma unroll 4
+      for (ll r = r_lo; r < r_hi; ++r, p += d) {
+        TV v[W];
+        loadW<TA, TV, W, NT>(p, v);
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+          const double dv = (double)v[k];
+          s[k] += dv;
+          q[k] = fma(dv, dv, q[k]);
+          lo[k] = (v[k] < lo[k]) ? v[k] : lo[k];
+          hi[k] = (v[k] > hi[k]) ? v[k] : hi[k];
+          nz[k] += (v[k] != (TV)0) ? 1 : 0;
+        }
+      }
+    } else {
+      for (ll r = r_lo; r < r_hi; ++r) {
+        const TA* __restrict__ p = A + r * d + c0;
+#pragma unroll
+        for (int k = 0; k < W; ++k)
+          if (c0 + k < d) {
+            TV v[1];
+            loadW<TA, TV, 1>(p + k, v);
+            const double dv = (double)v[0];
+            s[k] += dv;
+            q[k] = fma(dv, dv, q[k]);
+            lo[k] = (v[0] < lo[k]) ? v[0] : lo[k];
+            hi[k] = (v[0] > hi[k]) ? v[0] : hi[k];
+            nz[k] += (v[0] != (TV)0) ? 1 : 0;
+          }
+      }
+    }
+    const ll o = rb * d + c0;
+#pragma unroll
+    for (int k = 0; k < W; ++k)
+      if (full || c0 + k < d) {
+        psum[o + k] = s[k];
+        psumsq[o + k] = q[k];
+        pmin[o + k] = (float)lo[k];
+        pmax[o + k] = (float)hi[k];
+        pnnz[o + k] = nz[k];
+      }
+  }
+}
+
+// Fixed-order reduce of the row-block partial slabs (thread per column).
+__global__ __launch_bounds__(BLOCK) void k_colstats_reduce(
+    const double* __restrict__ psum, const double* __restrict__ psumsq,
+    const float* __restrict__ pmin, const float* __restrict__ pmax,
+    const int* __restrict__ pnnz, ll n_rb, ll d, double* __restrict__ sum,
+    double* __restrict__ sumsq, float* __restrict__ mn, float* __restrict__ mx,
+    ll* __restrict__ nnz) {
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll c = (ll)blockIdx.x * BLOCK + threadIdx.x; c < d; c += stride) {
+    double s = 0.0, q = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+    ll nz = 0;
+    for (ll rb = 0; rb < n_rb; ++rb) {
+      const ll o = rb * d + c;
+      s += psum[o];
+      q += psumsq[o];
+      lo = fminf(lo, pmin[o]);
+      hi = fmaxf(hi, pmax[o]);
+      nz += pnnz[o];
+    }
+    sum[c] = s;
+    sumsq[c] = q;
+    mn[c] = lo;
+    mx[c] = hi;
+    nnz[c] = nz;
+  }
+}
+
+// Sparse column moments over the CSC copy, stored entries only (the caller
+// folds the implicit zeros into min/max). Same light/heavy split as the CSC
+// gradient: thread per column up to heavy_T entries ...
+__global__ __launch_bounds__(BLOCK) void k_csc_colstats_light(
+    const int* __restrict__ colptr, const float* __restrict__ val, ll d,
+    int heavy_T, double* __restrict__ sum, double* __restrict__ sumsq,
+    float* __restrict__ mn, float* __restrict__ mx, ll* __restrict__ nnz) {
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll c = (ll)blockIdx.x * BLOCK + threadIdx.x; c < d; c += stride) {
+    const int k_lo = colptr[c], k_hi = colptr[c + 1];
+    if (k_hi - k_lo > heavy_T) continue;  // heavy path owns column c
+    double s = 0.0, q = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+    int nz = 0;
+    for (int k = k_lo; k < k_hi; ++k) {
+      const float v = val[k];
+      const double dv = (double)v;
+      s += dv;
+      q = fma(dv, dv, q);
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+      nz += (v != 0.f) ? 1 : 0;
+    }
+    sum[c] = s;
+    sumsq[c] = q;
+    mn[c] = lo;
+    mx[c] = hi;
+    nnz[c] = nz;
+  }
+}
+
+__device__ __forceinline__ float wave_reduce_min(float v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = fminf(v, __shfl_xor(v, off, WAVE));
+  return v;
+}
+
+// ... wave per S-entry task of a heavy column (lane-strided window, shuffle
+// reduction), one partial record per task ...
+__global__ __launch_bounds__(BLOCK) void k_csc_colstats_heavy_partial(
+    const int* __restrict__ colptr, const float* __restrict__ val,
+    const int* __restrict__ heavy_cols, const int* __restrict__ taskptr,
+    const int* __restrict__ task_heavy_idx, ll n_tasks, int S,
+    double* __restrict__ psum, double* __restrict__ psumsq,
+    float* __restrict__ pmin, float* __restrict__ pmax,
+    int* __restrict__ pnnz) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + wid;
+  const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
+  for (ll t = wave_gid; t < n_tasks; t += n_waves) {
+    const int i = task_heavy_idx[t];
+    const int c = heavy_cols[i];
+    const int c_lo = colptr[c], c_hi = colptr[c + 1];
+    const int k_lo = c_lo + (int)(t - taskptr[i]) * S;
+    const int k_hi = min(k_lo + S, c_hi);
+    double s = 0.0, q = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+    int nz = 0;
+    for (int k = k_lo + lane; k < k_hi; k += WAVE) {
+      const float v = val[k];
+      const double dv = (double)v;
+      s += dv;
+      q = fma(dv, dv, q);
+      lo = fminf(lo, v);
+      hi = fmaxf(hi, v);
+      nz += (v != 0.f) ? 1 : 0;
+    }
+    s = wave_reduce_sum(s);
+    q = wave_reduce_sum(q);
+    lo = wave_reduce_min(lo);
+    hi = wave_reduce_max(hi);
+    nz = wave_reduce_sum(nz);
+    if (lane == 0) {
+      psum[t] = s;
+      psumsq[t] = q;
+      pmin[t] = lo;
+      pmax[t] = hi;
+      pnnz[t] = nz;
+    }
+  }
+}
+
+// ... and a wave per heavy column combining its task partials in a fixed
+// order (lane-strided + the shuffle tree), as k_csc_heavy_combine does.
+__global__ __launch_bounds__(BLOCK) void k_csc_colstats_heavy_combine(
+    const int* __restrict__ heavy_cols, const int* __restrict__ taskptr,
+    const double* __restrict__ psum, const double* __restrict__ psumsq,
+    const float* __restrict__ pmin, const float* __restrict__ pmax,
+    const int* __restrict__ pnnz, ll n_heavy, double* __restrict__ sum,
+    double* __restrict__ sumsq, float* __restrict__ mn, float* __restrict__ mx,
+    ll* __restrict__ nnz) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + wid;
+  const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
+  for (ll i = wave_gid; i < n_heavy; i += n_waves) {
+    const int t_lo = taskptr[i], t_hi = taskptr[i + 1];
+    double s = 0.0, q = 0.0;
+    float lo = INFINITY, hi = -INFINITY;
+    ll nz = 0;
+    for (int t = t_lo + lane; t < t_hi; t += WAVE) {
+      s += psum[t];
+      q += psumsq[t];
+      lo = fminf(lo, pmin[t]);
+      hi = fmaxf(hi, pmax[t]);
+      nz += pnnz[t];
+    }
+    s = wave_reduce_sum(s);
+    q = wave_reduce_sum(q);
+    lo = wave_reduce_min(lo);
+    hi = wave_reduce_max(hi);
+    nz = wave_reduce_sum(nz);
+    if (lane == 0) {
+      const int c = heavy_cols[i];
+      sum[c] = s;
+      sumsq[c] = q;
+      mn[c] = lo;
+      mx[c] = hi;
+      nnz[c] = nz;
+    }
+  }
+}
+
+// Storage-type conversions for the scaling kernel. bf16 rounds to nearest
+// even with NaN kept NaN, so the result is bit-identical to torch's
+// (A.float() * s).to(torch.bfloat16).
+template <typename T, typename TC>
+__device__ __forceinline__ T scale_store(TC v) { return (T)v; }
+template <>
+__device__ __forceinline__ ubf16 scale_store<ubf16, float>(float v) {
+  return (v != v) ? (ubf16)0x7FC0 : f2bf_rne(v);
+}
+
+// out[r, c] = T(TC(A[r, c]) * s[c]) over the flat row-major array; out may
+// alias A (each thread reads its 16-B chunk before writing the same chunk,
+// hence no __restrict__ on A / out). VEC: d is a multiple of the 16-B chunk
+// and all pointers are 16-B aligned, so a chunk never straddles a row and
+// its W scale factors are one aligned vector load; otherwise elementwise.
+template <typename T, typename TC, bool VEC>
+__global__ __launch_bounds__(BLOCK) void k_dense_scale_cols(
+    const T* A, const TC* __restrict__ s, ll total, ll d, T* out) {
+  constexpr int VE = 16 / sizeof(T);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  if constexpr (VEC) {
+    const ll nv = total / VE;  // exact: d % VE == 0
+    for (ll i = gid; i < nv; i += stride) {
+      const ll e = i * VE;
+      const ll c = e % d;
+      TC v[VE], sv[VE];
+      loadW<T, TC, VE, false>(A + e, v);
+      loadAcc<TC, VE>(s + c, sv);
+      if constexpr (sizeof(T) == 2) {
+        using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
+        u16x8 o;
+#pragma unroll
+        for (int k = 0; k < VE; ++k) o[k] = scale_store<T, TC>(v[k] * sv[k]);
+        *(u16x8*)(out + e) = o;
+      } else {
+        TC o[VE];
+#pragma unroll
+        for (int k = 0; k < VE; ++k) o[k] = v[k] * sv[k];
+        storeAcc<TC, VE>((TC*)(out + e), o);
+      }
+    }
+  } else {
+    for (ll e = gid; e < total; e += stride) {
+      TC v[1];
+      loadW<T, TC, 1>(A + e, v);
+      out[e] = scale_store<T, TC>(v[0] * s[e % d]);
+    }
+  }
+}
+
+// CSR values: out[k] = val[k] * s[col[k]] (elementwise; out may alias val).
+__global__ __launch_bounds__(BLOCK) void k_csr_scale_vals(
+    const int* __restrict__ col, const float* val, const float* __restrict__ s,
+    ll nnz, float* out) {
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll k = (ll)blockIdx.x * BLOCK + threadIdx.x; k < nnz; k += stride)
+    out[k] = val[k] * s[col[k]];
+}
+
+// Largest column c in [lo, hi] with colptr[c] <= k (k < colptr[hi + 1]); the
+// upper-bound form skips empty columns.
+__device__ __forceinline__ ll csc_col_of(const int* __restrict__ colptr, ll lo,
+                                         ll hi, int k) {
+  while (lo < hi) {
+    const ll mid = (lo + hi + 1) >> 1;
+    if (colptr[mid] <= k) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+// CSC values: out[k] = val[k] * s[c] for k in column c. Element-parallel with
+// a search over colptr, so a hot column costs no more than its share of the
+// entries (a thread-per-column loop would serialise on it): each thread owns
+// 4 consecutive entries, searches the columns of the first and the last one
+// (the second search starts at the first result) and resolves the middle two
+// inside that range — free when all four share a column, the common case
+// inside a hot column. The same single f32 multiply as k_csr_scale_vals, so
+// the CSR and CSC values keep describing the same matrix bit for bit.
+__global__ __launch_bounds__(BLOCK) void k_csc_scale_vals(
+    const int* __restrict__ colptr, const float* val,
+    const float* __restrict__ s, ll nnz, ll d, float* out) {
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll ngroups = (nnz + 3) / 4;
+  for (ll g = (ll)blockIdx.x * BLOCK + threadIdx.x; g < ngroups; g += stride) {
+    const ll k0 = g * 4;
+    const int cnt = (int)((nnz - k0 < 4) ? (nnz - k0) : 4);
+    const ll c_first = csc_col_of(colptr, 0, d - 1, (int)k0);
+    const ll c_last = csc_col_of(colptr, c_first, d - 1, (int)(k0 + cnt - 1));
+    for (int j = 0; j < cnt; ++j) {
+      const ll c = (j == 0) ? c_first
+                   : (j == cnt - 1) ? c_last
+                   : csc_col_of(colptr, c_first, c_last, (int)(k0 + j));
+      out[k0 + j] = val[k0 + j] * s[c];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // K6: axpby  out = a*x + b*y
 // ---------------------------------------------------------------------------
 
@@ -2269,6 +2614,209 @@ extern "C" int agd_dot_diff(const void* x, const void* y, const void* gx,
   }
   hipLaunchKernelGGL((k_reduce_partials<1>), dim3(1), dim3(BLOCK), 0, s,
                      (double*)red_ws, grid, (double*)out);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Column statistics / column scaling entry points
+// ---------------------------------------------------------------------------
+
+// Bytes of partial workspace per (row block, column) of the dense statistics
+// pass: two f64 sums, f32 min and max, i32 non-zero count.
+#define COLSTATS_PART_BYTES 28
+
+// Row blocks of the dense statistics pass: the A^T·m plan, halved until the
+// (wider) statistics partials fit the same 512 MiB workspace bound.
+extern "C" long long agd_colstats_rowblocks(long long n, long long d,
+                                            int a_dtype) {
+  ll n_rb = agd_dense_rowblocks(n, d, a_dtype);
+  while (n_rb > 1 && n_rb * d * COLSTATS_PART_BYTES > (512LL << 20)) n_rb /= 2;
+  return n_rb;
+}
+
+template <typename TA, int W>
+static int dense_colstats_t(const void* A, ll n, ll d, ll n_rb, double* psum,
+                            double* psumsq, float* pmin, float* pmax,
+                            int* pnnz, double* sum, double* sumsq, float* mn,
+                            float* mx, ll* nnz, int nt_loads, hipStream_t s) {
+  const ll cols_per_block = (ll)BLOCK * W;
+  const ll n_cs = (d + cols_per_block - 1) / cols_per_block;
+  const int grid = grid_for(n_rb * n_cs, 1);
+  if (nt_loads)
+    hipLaunchKernelGGL((k_dense_colstats<TA, W, true>), dim3(grid), dim3(BLOCK),
+                       0, s, (const TA*)A, n, d, n_rb, psum, psumsq, pmin, pmax,
+                       pnnz);
+  else
+    hipLaunchKernelGGL((k_dense_colstats<TA, W, false>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const TA*)A, n, d, n_rb, psum,
+                       psumsq, pmin, pmax, pnnz);
+  const int grid2 = grid_for(d, BLOCK);
+  hipLaunchKernelGGL(k_colstats_reduce, dim3(grid2), dim3(BLOCK), 0, s, psum,
+                     psumsq, pmin, pmax, pnnz, n_rb, d, sum, sumsq, mn, mx,
+                     nnz);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Per-column sum / sum of squares (f64 [d]), min / max (f32 [d]) and non-zero
+// count (i64 [d]) of a row-major dense shard A[n, d], n >= 1. p* are the
+// n_rb * d partial slabs (n_rb from agd_colstats_rowblocks). All outputs are
+// overwritten.
+extern "C" int agd_dense_colstats(const void* A, int a_dtype, long long n,
+                                  long long d, long long n_rb, void* psum,
+                                  void* psumsq, void* pmin, void* pmax,
+                                  void* pnnz, void* sum, void* sumsq, void* mn,
+                                  void* mx, void* nnz, int nt_loads,
+                                  void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 1 || d < 1 || n_rb < 1 || n_rb > n) {
+    snprintf(g_err, sizeof(g_err),
+             "agd_dense_colstats: bad shape n=%lld d=%lld n_rb=%lld", n, d,
+             n_rb);
+    return 2;
+  }
+  const int W = pick_w(a_dtype, d);
+#define COLSTATS_ARGS                                                          \
+  A, n, d, n_rb, (double*)psum, (double*)psumsq, (float*)pmin, (float*)pmax,   \
+      (int*)pnnz, (double*)sum, (double*)sumsq, (float*)mn, (float*)mx,        \
+      (ll*)nnz, nt_loads, s
+  switch (a_dtype * 10 + (W > 1 ? 1 : 0)) {
+    case 1:  return dense_colstats_t<ubf16, 8>(COLSTATS_ARGS);
+    case 0:  return dense_colstats_t<ubf16, 1>(COLSTATS_ARGS);
+    case 11: return dense_colstats_t<float, 4>(COLSTATS_ARGS);
+    case 10: return dense_colstats_t<float, 1>(COLSTATS_ARGS);
+    case 21: return dense_colstats_t<double, 2>(COLSTATS_ARGS);
+    case 20: return dense_colstats_t<double, 1>(COLSTATS_ARGS);
+    case 31: return dense_colstats_t<unsigned char, 16>(COLSTATS_ARGS);
+    case 30: return dense_colstats_t<unsigned char, 1>(COLSTATS_ARGS);
+  }
+#undef COLSTATS_ARGS
+  snprintf(g_err, sizeof(g_err), "agd_dense_colstats: bad dtype %d", a_dtype);
+  return 2;
+}
+
+// The same five per-column quantities over the stored entries of a CSC copy
+// (colptr [d+1] i32, val [nnz] f32). Columns above heavy_T entries use the
+// heavy-task structure (n_tasks partial records p*); pass heavy_T = INT_MAX
+// and n_tasks = 0 for a plain thread-per-column pass. Outputs overwritten.
+extern "C" int agd_csc_colstats(const void* colptr, const void* val,
+                                long long d, int heavy_T,
+                                const void* heavy_cols, const void* taskptr,
+                                const void* task_heavy_idx, long long n_heavy,
+                                long long n_tasks, int S, void* psum,
+                                void* psumsq, void* pmin, void* pmax,
+                                void* pnnz, void* sum, void* sumsq, void* mn,
+                                void* mx, void* nnz, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (d < 1 || (n_tasks > 0 && (S < 1 || n_heavy < 1))) {
+    snprintf(g_err, sizeof(g_err),
+             "agd_csc_colstats: bad arguments d=%lld n_tasks=%lld S=%d", d,
+             n_tasks, S);
+    return 2;
+  }
+  {
+    const int grid = grid_for(d, BLOCK);
+    hipLaunchKernelGGL(k_csc_colstats_light, dim3(grid), dim3(BLOCK), 0, s,
+                       (const int*)colptr, (const float*)val, d, heavy_T,
+                       (double*)sum, (double*)sumsq, (float*)mn, (float*)mx,
+                       (ll*)nnz);
+  }
+  if (n_tasks > 0) {
+    const int grid = grid_for(n_tasks, WAVES_PER_BLOCK);
+    hipLaunchKernelGGL(k_csc_colstats_heavy_partial, dim3(grid), dim3(BLOCK), 0,
+                       s, (const int*)colptr, (const float*)val,
+                       (const int*)heavy_cols, (const int*)taskptr,
+                       (const int*)task_heavy_idx, n_tasks, S, (double*)psum,
+                       (double*)psumsq, (float*)pmin, (float*)pmax,
+                       (int*)pnnz);
+    const int grid2 = grid_for(n_heavy, WAVES_PER_BLOCK);
+    hipLaunchKernelGGL(k_csc_colstats_heavy_combine, dim3(grid2), dim3(BLOCK),
+                       0, s, (const int*)heavy_cols, (const int*)taskptr,
+                       (const double*)psum, (const double*)psumsq,
+                       (const float*)pmin, (const float*)pmax,
+                       (const int*)pnnz, n_heavy, (double*)sum, (double*)sumsq,
+                       (float*)mn, (float*)mx, (ll*)nnz);
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+static inline bool aligned16(const void* p) {
+  return ((uintptr_t)p & 15) == 0;
+}
+
+template <typename T, typename TC>
+static int dense_scale_cols_t(const void* A, const void* scale, ll n, ll d,
+                              void* out, hipStream_t s) {
+  constexpr int VE = 16 / sizeof(T);
+  const ll total = n * d;
+  const bool vec = (d % VE == 0) && aligned16(A) && aligned16(out) &&
+                   aligned16(scale);
+  if (vec) {
+    const int grid = grid_for(total / VE, BLOCK);
+    hipLaunchKernelGGL((k_dense_scale_cols<T, TC, true>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const T*)A, (const TC*)scale, total,
+                       d, (T*)out);
+  } else {
+    const int grid = grid_for(total, BLOCK);
+    hipLaunchKernelGGL((k_dense_scale_cols<T, TC, false>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const T*)A, (const TC*)scale, total,
+                       d, (T*)out);
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// out[r, c] = A[r, c] * scale[c] for a row-major A[n, d] (bf16 / f32 with an
+// f32 scale, f64 with an f64 scale); out may be A itself.
+extern "C" int agd_dense_scale_cols(const void* A, int a_dtype,
+                                    const void* scale, long long n,
+                                    long long d, void* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 1 || d < 1) {
+    snprintf(g_err, sizeof(g_err),
+             "agd_dense_scale_cols: bad shape n=%lld d=%lld", n, d);
+    return 2;
+  }
+  switch (a_dtype) {
+    case 0: return dense_scale_cols_t<ubf16, float>(A, scale, n, d, out, s);
+    case 1: return dense_scale_cols_t<float, float>(A, scale, n, d, out, s);
+    case 2: return dense_scale_cols_t<double, double>(A, scale, n, d, out, s);
+  }
+  snprintf(g_err, sizeof(g_err),
+           "agd_dense_scale_cols: unsupported dtype %d (scale before "
+           "quantising to fp8)", a_dtype);
+  return 2;
+}
+
+extern "C" int agd_csr_scale_vals(const void* col, const void* val,
+                                  const void* scale, long long nnz, void* out,
+                                  void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (nnz < 1) return 0;
+  const int grid = grid_for(nnz, BLOCK);
+  hipLaunchKernelGGL(k_csr_scale_vals, dim3(grid), dim3(BLOCK), 0, s,
+                     (const int*)col, (const float*)val, (const float*)scale,
+                     nnz, (float*)out);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// colptr is [d+1] with colptr[d] == nnz.
+extern "C" int agd_csc_scale_vals(const void* colptr, const void* val,
+                                  const void* scale, long long nnz,
+                                  long long d, void* out, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (nnz < 1) return 0;
+  if (d < 1) {
+    snprintf(g_err, sizeof(g_err), "agd_csc_scale_vals: bad d=%lld", d);
+    return 2;
+  }
+  const int grid = grid_for((nnz + 3) / 4, BLOCK);
+  hipLaunchKernelGGL(k_csc_scale_vals, dim3(grid), dim3(BLOCK), 0, s,
+                     (const int*)colptr, (const float*)val,
+                     (const float*)scale, nnz, d, (float*)out);
   HIP_CHECK(hipGetLastError());
   return 0;
 }

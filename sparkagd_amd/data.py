@@ -176,8 +176,30 @@ class CSRShard:
     CSC_HEAVY_T = int(__import__("os").environ.get("SPARKAGD_CSC_HEAVY_T", "16"))
     CSC_TASK_S = int(__import__("os").environ.get("SPARKAGD_CSC_TASK_S", "128"))
 
-    def _build_csc_heavy(self):
-        colptr = self.csc[0].to(torch.int64)
+    @classmethod
+    def _from_parts(cls, src: "CSRShard", val: torch.Tensor,
+                    csc_val: Optional[torch.Tensor]) -> "CSRShard":
+        """New shard with the sparsity pattern of ``src`` and new values:
+        shares rowptr, col, labels, weights, colptr, the CSC rows and the
+        heavy-task structure with ``src`` (no re-sort); only ``val`` and the
+        CSC ``val`` differ. ``csc_val`` must hold ``val`` in CSC order."""
+        out = cls.__new__(cls)
+        out.rowptr, out.col, out.val = src.rowptr, src.col, val
+        out.labels, out._d = src.labels, src._d
+        out.sample_weight = src.sample_weight
+        out.csc = None
+        out.csc_heavy = None
+        if src.csc is not None:
+            out.csc = (src.csc[0], src.csc[1], csc_val)
+            # the task structure is shared; the scratch buffer is per shard
+            out.csc_heavy = dict(src.csc_heavy)
+            if out.csc_heavy.get("partial") is not None:
+                out.csc_heavy["partial"] = torch.empty_like(
+                    src.csc_heavy["partial"])
+        return out
+
+    def _build_csc_heavy(self, csc=None):
+        colptr = (self.csc if csc is None else csc)[0].to(torch.int64)
         counts = torch.diff(colptr)
         dev = self.val.device
         # NOTE a length-sorted visit order for the light kernel (to remove

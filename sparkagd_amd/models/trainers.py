@@ -10,7 +10,7 @@ with ``predict``.
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Union
 
 import torch
 
@@ -121,7 +121,25 @@ class _GLMTrainer:
         checkpoint_path: Optional[str] = None,
         checkpoint_every: int = 0,
         resume_from: Optional[str] = None,
+        feature_scaling: Union[bool, str] = False,
     ) -> LinearModel:
+        """Fit the model. ``feature_scaling`` (default ``False``: the data is
+        used as is) standardises the columns first, as MLlib's GLM trainers
+        do (``useFeatureScaling``): ``True`` fits a
+        :class:`~sparkagd_amd.stats.StandardScaler`, trains on an
+        out-of-place scaled copy of the shard (a second copy of a dense
+        shard's features, or of a CSR shard's two value arrays, lives for the
+        duration of training) and returns a model whose ``weights`` are
+        already mapped back to the original feature space, so ``predict`` on
+        raw features needs no scaler. ``"inplace"`` does the same but
+        overwrites the caller's shard — for shards near memory capacity. As in
+        MLlib the regulariser acts on the scaled-space weights, and the loss
+        history is the scaled-space objective. ``initial_weights`` are always
+        given in the original space."""
+        from ..stats import scaled_training_data
+
+        data, scaler, initial_weights = scaled_training_data(
+            data, feature_scaling, comm, initial_weights)
         cfg = config or AGDConfig()
         cfg.num_iterations = num_iterations
         cfg.reg_param = reg_param
@@ -136,6 +154,8 @@ class _GLMTrainer:
             wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
             initial_weights = torch.zeros(data.d, device=data.device, dtype=wdtype)
         w = opt.optimize(data, initial_weights)
+        if scaler is not None:
+            w = scaler.unscale_weights(w)
         return LinearModel(w, opt.loss_history, cls.LINK)
 
 
@@ -246,8 +266,18 @@ class SoftmaxRegressionWithAGD:
         initial_weights: Optional[torch.Tensor] = None,
         comm: Optional[Communicator] = None,
         config: Optional[AGDConfig] = None,
+        feature_scaling: Union[bool, str] = False,
     ) -> MultinomialModel:
+        """``feature_scaling``: ``False`` | ``True`` | ``"inplace"``, as in
+        the binary GLM trainers (column standardisation before optimising;
+        ``True`` holds a scaled copy of the features during training; the
+        regulariser acts on the scaled-space weights; returned weights and
+        ``initial_weights`` are in the original feature space)."""
+        from ..stats import scaled_training_data
         from .gradient import MultinomialLogisticGradient
+
+        data, scaler, initial_weights = scaled_training_data(
+            data, feature_scaling, comm, initial_weights, num_classes)
 
         cfg = config or AGDConfig()
         cfg.num_iterations = num_iterations
@@ -262,6 +292,8 @@ class SoftmaxRegressionWithAGD:
             initial_weights = torch.zeros(data.d * num_classes,
                                           device=data.device, dtype=wdtype)
         w = opt.optimize(data, initial_weights)
+        if scaler is not None:
+            w = scaler.unscale_weights(w, num_classes)
         return MultinomialModel(w, opt.loss_history, num_classes)
 
 
@@ -285,8 +317,18 @@ class _SGDTrainer:
         initial_weights: Optional[torch.Tensor] = None,
         comm: Optional[Communicator] = None,
         step_schedule: str = "sqrt",
+        feature_scaling: Union[bool, str] = False,
     ) -> LinearModel:
+        """``feature_scaling``: ``False`` | ``True`` | ``"inplace"``, as in
+        the AGD trainers (column standardisation before optimising; ``True``
+        holds a scaled copy of the features during training; the regulariser
+        acts on the scaled-space weights; returned weights and
+        ``initial_weights`` are in the original feature space)."""
         from ..optimizer import GradientDescent
+        from ..stats import scaled_training_data
+
+        data, scaler, initial_weights = scaled_training_data(
+            data, feature_scaling, comm, initial_weights)
 
         if updater is None:
             updater = SquaredL2Updater() if reg_param > 0 else SimpleUpdater()
@@ -298,6 +340,8 @@ class _SGDTrainer:
             wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
             initial_weights = torch.zeros(data.d, device=data.device, dtype=wdtype)
         w = opt.optimize(data, initial_weights)
+        if scaler is not None:
+            w = scaler.unscale_weights(w)
         return LinearModel(w, opt.loss_history, cls.LINK)
 
 

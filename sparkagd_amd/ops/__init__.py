@@ -205,6 +205,42 @@ def dot_diff(
     return reference.dot_diff(x, y, g_x, g_y)
 
 
+def dense_colstats(features: torch.Tensor):
+    """Per-column (sum f64, sumsq f64, min f32, max f32, nnz i64), each [d]."""
+    if _use_hip(features):
+        return _get_hip().dense_colstats(features)
+    return reference.dense_colstats(features)
+
+
+def csr_colstats(csc, n: int, d: int, csc_heavy=None):
+    """The dense_colstats tuple over the stored entries of a CSC copy
+    ``(colptr, row, val)``; implicit zeros are the caller's to fold in."""
+    if _use_hip(csc[2]):
+        return _get_hip().csr_colstats(csc, n, d, csc_heavy)
+    return reference.csr_colstats(csc, n, d, csc_heavy)
+
+
+def dense_scale_cols(features: torch.Tensor, scale: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if _use_hip(features):
+        return _get_hip().dense_scale_cols(features, scale, out)
+    return reference.dense_scale_cols(features, scale, out)
+
+
+def csr_scale_vals(col: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    if _use_hip(val):
+        return _get_hip().csr_scale_vals(col, val, scale, out)
+    return reference.csr_scale_vals(col, val, scale, out)
+
+
+def csc_scale_vals(colptr: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
+                   out: Optional[torch.Tensor] = None, csc_heavy=None) -> torch.Tensor:
+    if _use_hip(val):
+        return _get_hip().csc_scale_vals(colptr, val, scale, out, csc_heavy)
+    return reference.csc_scale_vals(colptr, val, scale, out, csc_heavy)
+
+
 __all__ = [
     "LOSS_LOGISTIC",
     "LOSS_LEAST_SQUARES",
@@ -226,6 +262,11 @@ __all__ = [
     "axpby",
     "fused_scalars",
     "dot_diff",
+    "dense_colstats",
+    "csr_colstats",
+    "dense_scale_cols",
+    "csr_scale_vals",
+    "csc_scale_vals",
     "hip_available",
     "reference",
 ]

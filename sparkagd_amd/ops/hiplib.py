@@ -91,6 +91,20 @@ def load() -> ctypes.CDLL:
     lib.agd_gram_state_update.argtypes = [P, P, P, P, D, D, D, D, LL, P, P, P, P, P, P]
     lib.agd_at_margin_update.restype = I
     lib.agd_at_margin_update.argtypes = [P, P, P, D, D, D, LL, I, P, P, P]
+    lib.agd_colstats_rowblocks.restype = LL
+    lib.agd_colstats_rowblocks.argtypes = [LL, LL, I]
+    lib.agd_dense_colstats.restype = I
+    lib.agd_dense_colstats.argtypes = [P, I, LL, LL, LL, P, P, P, P, P,
+                                       P, P, P, P, P, I, P]
+    lib.agd_csc_colstats.restype = I
+    lib.agd_csc_colstats.argtypes = [P, P, LL, I, P, P, P, LL, LL, I,
+                                     P, P, P, P, P, P, P, P, P, P, P]
+    lib.agd_dense_scale_cols.restype = I
+    lib.agd_dense_scale_cols.argtypes = [P, I, P, LL, LL, P, P]
+    lib.agd_csr_scale_vals.restype = I
+    lib.agd_csr_scale_vals.argtypes = [P, P, P, LL, P, P]
+    lib.agd_csc_scale_vals.restype = I
+    lib.agd_csc_scale_vals.argtypes = [P, P, P, LL, LL, P, P]
 
     _lib = lib
     return lib
@@ -744,3 +758,152 @@ def at_margin_update(zm_old: torch.Tensor, xm_old: torch.Tensor,
         _stream(zm_old))
     _check(rc)
     return zm_new, xm_new
+
+
+# ---------------------------------------------------------------------------
+# Column statistics / column scaling
+# ---------------------------------------------------------------------------
+
+def _colstats_out(d: int, dev):
+    return (torch.empty(d, dtype=torch.float64, device=dev),
+            torch.empty(d, dtype=torch.float64, device=dev),
+            torch.empty(d, dtype=torch.float32, device=dev),
+            torch.empty(d, dtype=torch.float32, device=dev),
+            torch.empty(d, dtype=torch.int64, device=dev))
+
+
+def _colstats_partials(m: int, dev):
+    """Workspace for m partial records: (sum, sumsq) f64, (min, max) f32,
+    nnz i32."""
+    return (torch.empty(m, dtype=torch.float64, device=dev),
+            torch.empty(m, dtype=torch.float64, device=dev),
+            torch.empty(m, dtype=torch.float32, device=dev),
+            torch.empty(m, dtype=torch.float32, device=dev),
+            torch.empty(m, dtype=torch.int32, device=dev))
+
+
+def dense_colstats(features: torch.Tensor):
+    """(sum f64, sumsq f64, min f32, max f32, nnz i64), each [d], of a dense
+    [n, d] shard in one pass (k_dense_colstats + k_colstats_reduce);
+    bitwise reproducible."""
+    lib = load()
+    assert features.is_cuda and features.is_contiguous() and features.ndim == 2
+    n, d = features.shape
+    if n == 0 or d == 0:
+        raise ValueError("dense_colstats needs a non-empty [n, d] matrix")
+    a_dtype = _DTYPE_CODE[features.dtype]
+    dev = features.device
+    n_rb = int(lib.agd_colstats_rowblocks(n, d, a_dtype))
+    part = _colstats_partials(n_rb * d, dev)
+    out = _colstats_out(d, dev)
+    rc = lib.agd_dense_colstats(
+        _ptr(features), a_dtype, n, d, n_rb, *[_ptr(t) for t in part],
+        *[_ptr(t) for t in out],
+        int(os.environ.get("SPARKAGD_NT_LOADS", "1")), _stream(features))
+    _check(rc)
+    return out
+
+
+def csr_colstats(csc, n: int, d: int, csc_heavy: Optional[dict] = None):
+    """The dense_colstats tuple over the STORED entries of a CSC copy
+    (colptr, row, val); empty columns report sum 0, min +inf, max -inf.
+    Heavy columns go through the shard's task split when ``csc_heavy`` is
+    given."""
+    lib = load()
+    colptr, _crow, cval = csc
+    assert cval.is_cuda and cval.dtype == torch.float32
+    if colptr.numel() != d + 1:
+        raise ValueError("colptr must be [d + 1]")
+    dev = cval.device
+    out = _colstats_out(d, dev)
+    if csc_heavy is not None and csc_heavy["task_idx"].numel() > 0:
+        n_tasks = csc_heavy["task_idx"].numel()
+        part = _colstats_partials(n_tasks, dev)
+        rc = lib.agd_csc_colstats(
+            _ptr(colptr), _ptr(cval), d, int(csc_heavy["heavy_T"]),
+            _ptr(csc_heavy["cols"]), _ptr(csc_heavy["taskptr"]),
+            _ptr(csc_heavy["task_idx"]), csc_heavy["cols"].numel(), n_tasks,
+            int(csc_heavy["S"]), *[_ptr(t) for t in part],
+            *[_ptr(t) for t in out], _stream(cval))
+    else:
+        rc = lib.agd_csc_colstats(
+            _ptr(colptr), _ptr(cval), d, 2**31 - 1, None, None, None, 0, 0, 1,
+            None, None, None, None, None, *[_ptr(t) for t in out],
+            _stream(cval))
+    _check(rc)
+    return out
+
+
+def dense_scale_cols(features: torch.Tensor, scale: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[r, c] = features[r, c] * scale[c] in the features dtype (bf16/f32
+    through an f32 product, f64 through f64); ``out`` may be ``features``."""
+    lib = load()
+    assert features.is_cuda and features.is_contiguous() and features.ndim == 2
+    if features.dtype == torch.float8_e4m3fn:
+        raise NotImplementedError(
+            "fp8 features cannot be rescaled in place of their quantisation: "
+            "scale the bf16/f32 data first, then quantise")
+    n, d = features.shape
+    if scale.numel() != d:
+        raise ValueError("scale must be [d]")
+    sdt = torch.float64 if features.dtype == torch.float64 else torch.float32
+    scale = scale.to(device=features.device, dtype=sdt).contiguous()
+    if out is None:
+        out = torch.empty_like(features)
+    elif (out.shape != features.shape or out.dtype != features.dtype
+          or not out.is_contiguous() or out.device != features.device):
+        raise ValueError("out must match features (shape, dtype, contiguous)")
+    if n == 0 or d == 0:
+        return out
+    rc = lib.agd_dense_scale_cols(_ptr(features), _DTYPE_CODE[features.dtype],
+                                  _ptr(scale), n, d, _ptr(out),
+                                  _stream(features))
+    _check(rc)
+    return out
+
+
+def _scale_vals_out(val: torch.Tensor, out: Optional[torch.Tensor]):
+    assert val.is_cuda and val.dtype == torch.float32 and val.is_contiguous()
+    if out is None:
+        return torch.empty_like(val)
+    if (out.shape != val.shape or out.dtype != val.dtype
+            or not out.is_contiguous() or out.device != val.device):
+        raise ValueError("out must match val (shape, dtype, contiguous)")
+    return out
+
+
+def csr_scale_vals(col: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[k] = val[k] * scale[col[k]] (one f32 multiply)."""
+    lib = load()
+    out = _scale_vals_out(val, out)
+    col = col.contiguous()
+    if col.dtype != torch.int32:
+        col = col.to(torch.int32)
+    scale = scale.to(device=val.device, dtype=torch.float32).contiguous()
+    rc = lib.agd_csr_scale_vals(_ptr(col), _ptr(val), _ptr(scale), val.numel(),
+                                _ptr(out), _stream(val))
+    _check(rc)
+    return out
+
+
+def csc_scale_vals(colptr: torch.Tensor, val: torch.Tensor,
+                   scale: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   csc_heavy: Optional[dict] = None) -> torch.Tensor:
+    """out[k] = val[k] * scale[c] for k in column c. Element-parallel with a
+    colptr search, so no task split is needed; ``csc_heavy`` is accepted for
+    symmetry with the other CSC entry points and not used."""
+    lib = load()
+    out = _scale_vals_out(val, out)
+    colptr = colptr.contiguous()
+    if colptr.dtype != torch.int32:
+        colptr = colptr.to(torch.int32)
+    d = colptr.numel() - 1
+    if scale.numel() != d:
+        raise ValueError("scale must be [d]")
+    scale = scale.to(device=val.device, dtype=torch.float32).contiguous()
+    rc = lib.agd_csc_scale_vals(_ptr(colptr), _ptr(val), _ptr(scale),
+                                val.numel(), d, _ptr(out), _stream(val))
+    _check(rc)
+    return out

@@ -302,3 +302,87 @@ def dot_diff(x: torch.Tensor, y: torch.Tensor, g_x: torch.Tensor, g_y: torch.Ten
     xy = x.to(torch.float64) - y.to(torch.float64)
     dg = g_x.to(torch.float64) - g_y.to(torch.float64)
     return (xy * dg).sum()
+
+
+# ---------------------------------------------------------------------------
+# Column statistics / column scaling oracles
+# ---------------------------------------------------------------------------
+
+def dense_colstats(features: torch.Tensor):
+    """Per-column (sum f64, sumsq f64, min f32, max f32, nnz i64) of a dense
+    [n, d] matrix, everything accumulated in f64 (Statistics.colStats
+    moments). An empty matrix reports min +inf / max -inf."""
+    a = features.to(torch.float64)
+    n, d = a.shape
+    if n == 0:
+        mn = torch.full((d,), float("inf"), dtype=torch.float32, device=a.device)
+        mx = -mn
+    else:
+        mn = a.amin(dim=0).to(torch.float32)
+        mx = a.amax(dim=0).to(torch.float32)
+    return (a.sum(dim=0), (a * a).sum(dim=0), mn, mx,
+            (a != 0).sum(dim=0).to(torch.int64))
+
+
+def _csc_cols(colptr: torch.Tensor) -> torch.Tensor:
+    d = colptr.numel() - 1
+    return torch.repeat_interleave(
+        torch.arange(d, device=colptr.device, dtype=torch.int64),
+        torch.diff(colptr.to(torch.int64)))
+
+
+def csr_colstats(csc, n: int, d: int, csc_heavy=None):
+    """The dense_colstats tuple over the STORED entries of a CSC copy
+    (colptr, row, val): empty columns report sum 0, min +inf, max -inf, and
+    the caller folds in the implicit zeros."""
+    colptr, _row, val = csc
+    cols = _csc_cols(colptr)
+    v = val.to(torch.float64)
+    dev = val.device
+    s = torch.zeros(d, dtype=torch.float64, device=dev).index_add_(0, cols, v)
+    q = torch.zeros(d, dtype=torch.float64, device=dev).index_add_(0, cols, v * v)
+    mn = torch.full((d,), float("inf"), dtype=torch.float64, device=dev)
+    mn.scatter_reduce_(0, cols, v, reduce="amin", include_self=True)
+    mx = torch.full((d,), float("-inf"), dtype=torch.float64, device=dev)
+    mx.scatter_reduce_(0, cols, v, reduce="amax", include_self=True)
+    nnz = torch.zeros(d, dtype=torch.int64, device=dev).index_add_(
+        0, cols, (v != 0).to(torch.int64))
+    return s, q, mn.to(torch.float32), mx.to(torch.float32), nnz
+
+
+def _scale_acc(dtype: torch.dtype) -> torch.dtype:
+    return torch.float64 if dtype == torch.float64 else torch.float32
+
+
+def dense_scale_cols(features: torch.Tensor, scale: torch.Tensor,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """features * scale[None, :] through one multiply in f32 (f64 for f64
+    features), rounded back to the features dtype."""
+    if features.dtype == torch.float8_e4m3fn:
+        raise NotImplementedError(
+            "fp8 features cannot be rescaled in place of their quantisation: "
+            "scale the bf16/f32 data first, then quantise")
+    acc = _scale_acc(features.dtype)
+    res = (features.to(acc) * scale.to(device=features.device, dtype=acc)).to(features.dtype)
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def csr_scale_vals(col: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    res = val * scale.to(device=val.device, dtype=val.dtype)[col.to(torch.int64)]
+    if out is None:
+        return res
+    out.copy_(res)
+    return out
+
+
+def csc_scale_vals(colptr: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
+                   out: Optional[torch.Tensor] = None, csc_heavy=None) -> torch.Tensor:
+    res = val * scale.to(device=val.device, dtype=val.dtype)[_csc_cols(colptr)]
+    if out is None:
+        return res
+    out.copy_(res)
+    return out

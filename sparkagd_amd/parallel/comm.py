@@ -49,10 +49,16 @@ class Communicator:
             return 0
         return dist.get_rank(self.group)
 
-    def allreduce_(self, t: torch.Tensor) -> torch.Tensor:
-        """In-place sum all-reduce (no-op at world size 1)."""
+    _REDUCE_OPS = {"sum": dist.ReduceOp.SUM, "min": dist.ReduceOp.MIN,
+                   "max": dist.ReduceOp.MAX}
+
+    def allreduce_(self, t: torch.Tensor, op: str = "sum") -> torch.Tensor:
+        """In-place all-reduce (no-op at world size 1); ``op`` is "sum"
+        (default), "min" or "max"."""
+        if op not in self._REDUCE_OPS:
+            raise ValueError(f"allreduce_ op must be sum|min|max, got {op!r}")
         if self._active and self.world_size > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+            dist.all_reduce(t, op=self._REDUCE_OPS[op], group=self.group)
         return t
 
     def allreduce_eval_(self, grad_sum: torch.Tensor, loss_count: torch.Tensor):
