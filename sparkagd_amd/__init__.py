@@ -44,6 +44,8 @@ from .optimizer import (AcceleratedGradientDescent, GradientDescent, run,
 from .gram import GramOperator, run_gram
 from .parallel.comm import Communicator
 from . import evaluation
+from .evaluation import (BinaryMetrics, MulticlassMetrics, RegressionMetrics,
+                         evaluate)
 from .streaming import HostStreamedDenseShard
 from .stats import ColumnSummary, StandardScaler, column_stats
 
@@ -91,4 +93,8 @@ __all__ = [
     "ColumnSummary",
     "StandardScaler",
     "column_stats",
+    "evaluate",
+    "BinaryMetrics",
+    "RegressionMetrics",
+    "MulticlassMetrics",
 ]

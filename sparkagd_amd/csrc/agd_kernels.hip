@@ -2820,3 +2820,322 @@ extern "C" int agd_csc_scale_vals(const void* colptr, const void* val,
   HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Evaluation metrics: one fused pass from margins, labels and optional sample
+// weights to every sufficient statistic the host needs for ROC/PR curves,
+// the confusion at a cut and the mean losses (sparkagd_amd/evaluation.py).
+//
+// Counts are INTEGERS: an unweighted example adds 1, a weighted one adds
+// llrint(w * 2^32), a 2^-32 fixed-point count. Integer addition is
+// associative, so LDS and global integer atomics give the same bits whatever
+// order the hardware serves them in — the float atomics this library avoids
+// everywhere (see block_reduce_partial) would not. The f64 sums go through
+// block_reduce_partial / k_reduce_partials like every other scalar here.
+//
+// Per block: the histogram lives in LDS (64-bit ds atomics), is flushed with
+// one global 64-bit atomic per non-empty bin, and the handful of same-address
+// counters (confusion, NaN count, weight minimum) leave as a per-block
+// partial row that k_reduce_counts sums — a few thousand blocks hammering
+// five words would serialise, the hist bins spread over 2B words do not.
+// ---------------------------------------------------------------------------
+
+#define METRICS_NSUM 7        // Σw, Σw·logloss, Σw·(z−y)², Σw·|z−y|, Σw·y, Σw·y², Σw·(z−y)
+#define METRICS_NCNT 5        // tp, fp, fn, tn, nan (+ 1 min slot after them)
+#define METRICS_MAX_BLOCKS 1024
+#define METRICS_BMAX_SMALL 1024
+#define METRICS_BMAX 4096
+#define METRICS_CONF_LDS 4096  // multiclass confusion cells kept in LDS (K <= 64)
+
+typedef unsigned long long ull;
+
+// Block-level integer reduction: NSUM sums followed by one signed minimum,
+// written to part[blockIdx.x * (NSUM + 1) + k].
+template <int NSUM>
+__device__ __forceinline__ void block_reduce_counts(ll (&c)[NSUM + 1],
+                                                    ll* __restrict__ part) {
+  __shared__ ll lds[WAVES_PER_BLOCK][NSUM + 1];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+#pragma unroll
+  for (int k = 0; k <= NSUM; ++k) {
+    ll v = c[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const ll o = __shfl_xor(v, off, WAVE);
+      v = (k < NSUM) ? v + o : (o < v ? o : v);
+    }
+    if (lane == 0) lds[wid][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x <= NSUM) {
+    const int k = threadIdx.x;
+    ll v = lds[0][k];
+#pragma unroll
+    for (int w = 1; w < WAVES_PER_BLOCK; ++w) {
+      const ll o = lds[w][k];
+      v = (k < NSUM) ? v + o : (o < v ? o : v);
+    }
+    part[(ll)blockIdx.x * (NSUM + 1) + k] = v;
+  }
+}
+
+// One block folds the per-block count rows into out[NSUM + 1] (overwrites).
+template <int NSUM>
+__global__ __launch_bounds__(BLOCK) void k_reduce_counts(
+    const ll* __restrict__ part, int nblocks, ll* __restrict__ out) {
+  ll c[NSUM + 1];
+#pragma unroll
+  for (int k = 0; k < NSUM; ++k) c[k] = 0;
+  c[NSUM] = 0x7fffffffffffffffll;
+  for (int i = threadIdx.x; i < nblocks; i += BLOCK) {
+#pragma unroll
+    for (int k = 0; k < NSUM; ++k) c[k] += part[(ll)i * (NSUM + 1) + k];
+    const ll m = part[(ll)i * (NSUM + 1) + NSUM];
+    if (m < c[NSUM]) c[NSUM] = m;
+  }
+  block_reduce_counts<NSUM>(c, out);  // gridDim.x == 1: row 0 is out itself
+}
+
+// Weight as a 2^-32 fixed-point integer, and its running minimum tracked on
+// the raw float bits: as SIGNED integers the bit patterns of non-negative
+// floats order like the floats, and every negative float (and -NaN) is a
+// negative integer, so min >= 0 on the host proves every weight was >= 0.
+__device__ __forceinline__ ll weight_units(float w, ll& wmin_bits) {
+  const ll bits = (ll)__float_as_int(w);
+  if (bits < wmin_bits) wmin_bits = bits;
+  return llrint((double)w * 4294967296.0);
+}
+
+// ints layout (int64): hist_pos[nbins] | hist_neg[nbins] | tp fp fn tn | nan |
+// min weight bits. The caller zeroes the 2*nbins histogram words; the six
+// trailing words are overwritten by k_reduce_counts.
+template <typename TACC, int BMAX>
+__global__ __launch_bounds__(BLOCK) void k_binary_metrics(
+    const TACC* __restrict__ margins, const float* __restrict__ labels,
+    const float* __restrict__ sample_weight, const TACC* __restrict__ edges,
+    int nbins, TACC cut, ll n, ull* __restrict__ hist,
+    ll* __restrict__ cnt_part, double* __restrict__ red_part) {
+  __shared__ ull s_hist[2 * BMAX];
+  __shared__ TACC s_edges[BMAX];
+  const int ne = nbins - 1;
+  for (int j = threadIdx.x; j < 2 * nbins; j += BLOCK) s_hist[j] = 0ull;
+  for (int j = threadIdx.x; j < ne; j += BLOCK) s_edges[j] = edges[j];
+  __syncthreads();
+
+  double acc[METRICS_NSUM];
+#pragma unroll
+  for (int k = 0; k < METRICS_NSUM; ++k) acc[k] = 0.0;
+  ll cnt[METRICS_NCNT + 1] = {0, 0, 0, 0, 0, 0x7fffffffffffffffll};
+
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll i = (ll)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+    const TACC z = margins[i];
+    const float yf = labels[i];
+    ll u = 1;
+    double w = 1.0;
+    if (sample_weight) {
+      const float wf = sample_weight[i];
+      u = weight_units(wf, cnt[METRICS_NCNT]);
+      w = (double)wf;
+    }
+    if (z != z) {  // NaN margins are counted and otherwise left out
+      cnt[4] += 1;
+      continue;
+    }
+    // bin = number of edges <= z, by comparisons only (bit-exact against
+    // torch.bucketize(right=True); +-inf land in the end bins)
+    int lo = 0, hi = ne;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (s_edges[mid] <= z) lo = mid + 1; else hi = mid;
+    }
+    const bool pos = yf > 0.5f;
+    atomicAdd(&s_hist[(pos ? 0 : nbins) + lo], (ull)u);
+    const bool pred = z > cut;
+    cnt[pos ? (pred ? 0 : 2) : (pred ? 1 : 3)] += u;
+
+    const double zd = (double)z, yd = (double)yf;
+    const double ls = pos ? softplus<double>(-zd) : softplus<double>(zd);
+    const double diff = zd - yd;
+    acc[0] += w;
+    acc[1] += w * ls;
+    acc[2] += w * (diff * diff);
+    acc[3] += w * fabs(diff);
+    acc[4] += w * yd;
+    acc[5] += w * (yd * yd);
+    acc[6] += w * diff;
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < 2 * nbins; j += BLOCK) {
+    const ull v = s_hist[j];
+    if (v) atomicAdd(&hist[j], v);
+  }
+  block_reduce_counts<METRICS_NCNT>(cnt, cnt_part);
+  block_reduce_partial<METRICS_NSUM>(acc, red_part);
+}
+
+// Multiclass: G lanes share a row (G = 1 for KC <= 32, a whole wave above).
+// Predicted class = argmax over the logical K, lowest index on ties; the
+// per-row softmax loss is computed as k_multiplier_multi does (max-subtracted
+// f32, accumulated in f64). conf is [K, K] int64, rows = true class, zeroed
+// by the caller; cnt_part rows are {labels outside [0, K), min weight bits}.
+template <int G>
+__global__ __launch_bounds__(BLOCK) void k_multiclass_metrics(
+    const float* __restrict__ Z, const float* __restrict__ labels,
+    const float* __restrict__ sample_weight, ll n, int K, int KC,
+    ull* __restrict__ conf, ll* __restrict__ cnt_part,
+    double* __restrict__ red_part) {
+  __shared__ ull s_conf[METRICS_CONF_LDS];
+  const bool in_lds = K * K <= METRICS_CONF_LDS;
+  if (in_lds) {
+    for (int j = threadIdx.x; j < K * K; j += BLOCK) s_conf[j] = 0ull;
+    __syncthreads();
+  }
+  const int sub = threadIdx.x % G;
+  const ll gid = ((ll)blockIdx.x * BLOCK + threadIdx.x) / G;
+  const ll ngroups = (ll)gridDim.x * (BLOCK / G);
+  double wsum = 0.0, lsum = 0.0;
+  ll cnt[2] = {0, 0x7fffffffffffffffll};
+  for (ll i = gid; i < n; i += ngroups) {
+    const float* __restrict__ zrow = Z + i * KC;
+    float best = -INFINITY;
+    int bi = 0;
+    for (int k = sub; k < K; k += G) {
+      const float v = zrow[k];
+      if (v > best) { best = v; bi = k; }
+    }
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1) {
+      const float ob = __shfl_xor(best, off, WAVE);
+      const int oi = __shfl_xor(bi, off, WAVE);
+      if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    float esum = 0.f;
+    for (int k = sub; k < K; k += G) esum += __expf(zrow[k] - best);
+#pragma unroll
+    for (int off = G / 2; off > 0; off >>= 1)
+      esum += __shfl_xor(esum, off, WAVE);
+    if (sub == 0) {
+      const int y = (int)labels[i];
+      const bool valid = y >= 0 && y < K;
+      ll u = 1;
+      double w = 1.0;
+      if (sample_weight) {
+        const float wf = sample_weight[i];
+        u = weight_units(wf, cnt[1]);
+        w = (double)wf;
+      }
+      // max-subtracted like k_multiplier_multi, but with the maximum taken
+      // out of z_y too: (logf(esum) + best) - z_y cancels to a few ulp of
+      // |best| on a confident correct row, logf(esum) + (best - z_y) does not
+      const float loss = logf(esum) + (best - (valid ? zrow[y] : 0.f));
+      wsum += w;
+      lsum += w * (double)loss;
+      if (!valid) {
+        cnt[0] += 1;
+      } else if (in_lds) {
+        atomicAdd(&s_conf[y * K + bi], (ull)u);
+      } else {
+        atomicAdd(&conf[(ll)y * K + bi], (ull)u);
+      }
+    }
+  }
+  if (in_lds) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < K * K; j += BLOCK) {
+      const ull v = s_conf[j];
+      if (v) atomicAdd(&conf[j], v);
+    }
+  }
+  block_reduce_counts<1>(cnt, cnt_part);
+  double acc[2] = {wsum, lsum};
+  block_reduce_partial<2>(acc, red_part);
+}
+
+// Workspace sizing for the two entry points below: cnt_ws holds
+// agd_metrics_max_blocks() * 6 int64, red_ws the same number of rows of 7 f64.
+extern "C" int agd_metrics_max_blocks() { return METRICS_MAX_BLOCKS; }
+
+// ints: int64[2*nbins + 6] (layout above k_binary_metrics) with the first
+// 2*nbins words zeroed by the caller; sums: f64[7], zeroed by the caller.
+// m_dtype: 1 = f32, 2 = f64 (margins and edges share it).
+extern "C" int agd_binary_metrics(const void* margins, int m_dtype,
+                                  const void* labels, const void* sample_weight,
+                                  const void* edges, int nbins, double cut,
+                                  long long n, void* ints, void* sums,
+                                  void* cnt_ws, void* red_ws, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (nbins < 1 || nbins > METRICS_BMAX) {
+    snprintf(g_err, sizeof(g_err), "binary_metrics: nbins %d not in [1, %d]",
+             nbins, METRICS_BMAX);
+    return 2;
+  }
+  if (m_dtype != 1 && m_dtype != 2) {
+    snprintf(g_err, sizeof(g_err), "binary_metrics: dtype %d unsupported",
+             m_dtype);
+    return 2;
+  }
+  // The big-histogram variant holds 64 + 16/32 KiB of LDS, one block per CU;
+  // a quarter of the blocks keeps its flush traffic level with the small one.
+  const bool small = nbins <= METRICS_BMAX_SMALL;
+  int grid = grid_for(n, BLOCK);
+  const int cap = small ? METRICS_MAX_BLOCKS : METRICS_MAX_BLOCKS / 4;
+  if (grid > cap) grid = cap;
+#define LAUNCH_BM(T, BM)                                                      \
+  hipLaunchKernelGGL((k_binary_metrics<T, BM>), dim3(grid), dim3(BLOCK), 0,   \
+                     s, (const T*)margins, (const float*)labels,              \
+                     (const float*)sample_weight, (const T*)edges, nbins,     \
+                     (T)cut, n, (ull*)ints, (ll*)cnt_ws, (double*)red_ws)
+  if (m_dtype == 1) {
+    if (small) LAUNCH_BM(float, METRICS_BMAX_SMALL);
+    else LAUNCH_BM(float, METRICS_BMAX);
+  } else {
+    if (small) LAUNCH_BM(double, METRICS_BMAX_SMALL);
+    else LAUNCH_BM(double, METRICS_BMAX);
+  }
+#undef LAUNCH_BM
+  hipLaunchKernelGGL((k_reduce_counts<METRICS_NCNT>), dim3(1), dim3(BLOCK), 0,
+                     s, (const ll*)cnt_ws, grid, (ll*)ints + 2 * (ll)nbins);
+  hipLaunchKernelGGL((k_reduce_partials<METRICS_NSUM>), dim3(1), dim3(BLOCK),
+                     0, s, (const double*)red_ws, grid, (double*)sums);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Z: f32 padded margins [n, kc]; ints: int64[k*k + 2] = confusion (zeroed by
+// the caller) | bad-label count | min weight bits; sums: f64[2] = {Σw,
+// Σw·loss}, zeroed by the caller.
+extern "C" int agd_multiclass_metrics(const void* Z, const void* labels,
+                                      const void* sample_weight, long long n,
+                                      int k, int kc, void* ints, void* sums,
+                                      void* cnt_ws, void* red_ws,
+                                      void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (k < 2 || kc < k) {
+    snprintf(g_err, sizeof(g_err), "multiclass_metrics: bad K=%d KC=%d", k, kc);
+    return 2;
+  }
+  int grid;
+#define LAUNCH_MM(GV)                                                         \
+  hipLaunchKernelGGL((k_multiclass_metrics<GV>), dim3(grid), dim3(BLOCK), 0,  \
+                     s, (const float*)Z, (const float*)labels,                \
+                     (const float*)sample_weight, n, k, kc, (ull*)ints,       \
+                     (ll*)cnt_ws, (double*)red_ws)
+  if (kc <= 32) {
+    grid = grid_for(n, BLOCK);
+    if (grid > METRICS_MAX_BLOCKS) grid = METRICS_MAX_BLOCKS;
+    LAUNCH_MM(1);
+  } else {
+    grid = grid_for(n, WAVES_PER_BLOCK);
+    if (grid > METRICS_MAX_BLOCKS) grid = METRICS_MAX_BLOCKS;
+    LAUNCH_MM(WAVE);
+  }
+#undef LAUNCH_MM
+  hipLaunchKernelGGL((k_reduce_counts<1>), dim3(1), dim3(BLOCK), 0, s,
+                     (const ll*)cnt_ws, grid, (ll*)ints + (ll)k * k);
+  hipLaunchKernelGGL((k_reduce_partials<2>), dim3(1), dim3(BLOCK), 0, s,
+                     (const double*)red_ws, grid, (double*)sums);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}

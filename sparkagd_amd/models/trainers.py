@@ -55,6 +55,29 @@ def _load_model(path: str, device=None):
     return w, meta
 
 
+def _shard_feature_dtype(shard) -> torch.dtype:
+    if getattr(shard, "kind", None) == "mixed":
+        dts = [_shard_feature_dtype(p) for p in shard.parts]
+        return torch.float64 if torch.float64 in dts else dts[0]
+    for attr in ("features", "features_host", "val"):
+        t = getattr(shard, attr, None)
+        if t is not None:
+            return t.dtype
+    raise TypeError(f"unsupported shard type {type(shard).__name__}")
+
+
+def _weights_for(shard, weights: torch.Tensor) -> torch.Tensor:
+    """The model weights placed and typed as ``shard.margins`` wants them:
+    on the shard's device, and on GPU in the kernels' accumulator dtype (f64
+    for f64 features, f32 for everything narrower)."""
+    dev = torch.device(shard.device)
+    w = weights.to(dev)
+    if dev.type == "cuda":
+        f64 = _shard_feature_dtype(shard) == torch.float64
+        w = w.to(torch.float64 if f64 else torch.float32)
+    return w.contiguous()
+
+
 class LinearModel:
     """A fitted generalized linear model: weights [d] (+ loss history).
     MLlib-style model persistence via ``save``/``load`` (safetensors)."""
@@ -101,6 +124,30 @@ class LinearModel:
         if self.link != "logistic":
             raise ValueError("predict_proba only for logistic models")
         return torch.sigmoid(self.margins(features))
+
+    def _cut(self, threshold: float) -> float:
+        """Margin-space cut of a probability threshold (see ``predict``)."""
+        import math as _math
+
+        if self.link == "logistic" and threshold != 0.5:
+            return _math.log(threshold / (1.0 - threshold))
+        return 0.0
+
+    def score(self, shard) -> torch.Tensor:
+        """Margins [n] of a whole shard of any kind (dense bf16 / f32 / f64 /
+        fp8, CSR, mixed, host-streamed) through the shard's own
+        ``margins`` kernels — the features are read in place, never copied
+        or widened."""
+        return shard.margins(_weights_for(shard, self.weights))
+
+    def predict_shard(self, shard,
+                      threshold: Optional[float] = 0.5) -> torch.Tensor:
+        """``predict`` over a shard: same thresholds, same strict ``z > cut``
+        comparison, margins from ``score``."""
+        z = self.score(shard)
+        if self.link == "identity" or threshold is None:
+            return z
+        return (z > self._cut(threshold)).to(torch.float32)
 
 
 class _GLMTrainer:
@@ -236,6 +283,26 @@ class MultinomialModel:
 
     def predict_proba(self, features: torch.Tensor) -> torch.Tensor:
         return torch.softmax(self.margins(features), dim=1)
+
+    def _score_padded(self, shard) -> torch.Tensor:
+        from .gradient import MultinomialLogisticGradient
+
+        return MultinomialLogisticGradient(self.num_classes).margins(
+            shard, _weights_for(shard, self.weights))
+
+    def score(self, shard) -> torch.Tensor:
+        """Margins of a whole dense or CSR shard as the logical [n, K] view
+        of the kernels' class-padded buffer; the features are read in place."""
+        from ..ops.multiclass import padded_k
+
+        zp = self._score_padded(shard)
+        return zp.reshape(shard.n, padded_k(self.num_classes))[:, :self.num_classes]
+
+    def predict_shard(self, shard, threshold: Optional[float] = 0.5) -> torch.Tensor:
+        """``predict`` over a shard (class indices as f32). ``threshold`` is
+        accepted for signature parity with ``LinearModel`` and has no effect
+        on an argmax."""
+        return self.score(shard).argmax(dim=1).to(torch.float32)
 
     def save(self, path: str) -> None:
         _save_model(path, self.weights,

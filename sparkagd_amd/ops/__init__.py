@@ -241,6 +241,18 @@ def csc_scale_vals(colptr: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
     return reference.csc_scale_vals(colptr, val, scale, out, csc_heavy)
 
 
+def binary_metrics(margins: torch.Tensor, labels: torch.Tensor,
+                   edges: torch.Tensor, cut: float,
+                   sample_weight: Optional[torch.Tensor] = None):
+    """One fused pass from margins / labels / weights to (hist_pos i64[B],
+    hist_neg i64[B], conf i64[4], sums f64[7], nan_count, min_weight); the
+    contract is spelled out on ``reference.binary_metrics``."""
+    if _use_hip(margins):
+        return _get_hip().binary_metrics(margins, labels, edges, cut,
+                                         sample_weight)
+    return reference.binary_metrics(margins, labels, edges, cut, sample_weight)
+
+
 __all__ = [
     "LOSS_LOGISTIC",
     "LOSS_LEAST_SQUARES",
@@ -267,6 +279,7 @@ __all__ = [
     "dense_scale_cols",
     "csr_scale_vals",
     "csc_scale_vals",
+    "binary_metrics",
     "hip_available",
     "reference",
 ]

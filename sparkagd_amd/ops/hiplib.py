@@ -105,6 +105,12 @@ def load() -> ctypes.CDLL:
     lib.agd_csr_scale_vals.argtypes = [P, P, P, LL, P, P]
     lib.agd_csc_scale_vals.restype = I
     lib.agd_csc_scale_vals.argtypes = [P, P, P, LL, LL, P, P]
+    lib.agd_metrics_max_blocks.restype = I
+    lib.agd_metrics_max_blocks.argtypes = []
+    lib.agd_binary_metrics.restype = I
+    lib.agd_binary_metrics.argtypes = [P, I, P, P, P, I, D, LL, P, P, P, P, P]
+    lib.agd_multiclass_metrics.restype = I
+    lib.agd_multiclass_metrics.argtypes = [P, P, P, LL, I, I, P, P, P, P, P]
 
     _lib = lib
     return lib
@@ -907,3 +913,90 @@ def csc_scale_vals(colptr: torch.Tensor, val: torch.Tensor,
                                 val.numel(), d, _ptr(out), _stream(val))
     _check(rc)
     return out
+
+
+_cnt_ws_cache = {}
+
+
+def _metrics_ws(device):
+    """(int64 count partials, f64 sum partials) for the metrics kernels: one
+    row per block, at most agd_metrics_max_blocks() rows of 6 / 7 words."""
+    rows = int(load().agd_metrics_max_blocks())
+    red = _red_ws(device)
+    assert red.numel() >= rows * 7
+    t = _cnt_ws_cache.get(device)
+    if t is None:
+        t = torch.empty(rows * 6, dtype=torch.int64, device=device)
+        _cnt_ws_cache[device] = t
+    return t, red
+
+
+def _min_weight(bits: torch.Tensor, weighted: bool, n: int) -> torch.Tensor:
+    """The kernels' min-weight word (sign-extended f32 bits) as an f32 0-dim."""
+    if not weighted or n == 0:
+        return torch.tensor(float("inf"), dtype=torch.float32,
+                            device=bits.device)
+    return bits.reshape(1).to(torch.int32).view(torch.float32)[0]
+
+
+def binary_metrics(margins: torch.Tensor, labels: torch.Tensor,
+                   edges: torch.Tensor, cut: float,
+                   sample_weight: Optional[torch.Tensor] = None):
+    """k_binary_metrics: (hist_pos, hist_neg, conf[4], sums f64[7], nan_count,
+    min_weight) — see ``reference.binary_metrics`` for the contract."""
+    lib = load()
+    if margins.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"margins must be f32 or f64, got {margins.dtype}")
+    z = margins.reshape(-1).contiguous()
+    n = z.numel()
+    dev = z.device
+    edges = edges.to(device=dev, dtype=z.dtype).reshape(-1).contiguous()
+    nbins = edges.numel() + 1
+    from .reference import METRICS_MAX_BINS
+
+    if nbins > METRICS_MAX_BINS:
+        raise ValueError(f"at most {METRICS_MAX_BINS} bins, got {nbins}")
+    labels = labels.to(device=dev, dtype=torch.float32).contiguous()
+    sw = _prep_weights(sample_weight, dev)
+    if labels.numel() != n or (sw is not None and sw.numel() != n):
+        raise ValueError("labels / sample_weight must match margins [n]")
+    ints = torch.zeros(2 * nbins + 6, dtype=torch.int64, device=dev)
+    sums = torch.zeros(7, dtype=torch.float64, device=dev)
+    cnt_ws, red_ws = _metrics_ws(dev)
+    rc = lib.agd_binary_metrics(
+        _ptr(z), _DTYPE_CODE[z.dtype], _ptr(labels), _ptr(sw), _ptr(edges),
+        nbins, float(cut), n, _ptr(ints), _ptr(sums), _ptr(cnt_ws),
+        _ptr(red_ws), _stream(z))
+    _check(rc)
+    b = nbins
+    return (ints[:b], ints[b:2 * b], ints[2 * b:2 * b + 4], sums,
+            ints[2 * b + 4], _min_weight(ints[2 * b + 5], sw is not None, n))
+
+
+def multiclass_metrics(margins_padded_flat: torch.Tensor, labels: torch.Tensor,
+                       k: int, kc: int,
+                       sample_weight: Optional[torch.Tensor] = None):
+    """k_multiclass_metrics: (conf [k, k], sums f64[2], bad_labels,
+    min_weight) — see ``reference.multiclass_metrics``."""
+    lib = load()
+    z = margins_padded_flat.reshape(-1)
+    if z.dtype != torch.float32:
+        z = z.to(torch.float32)
+    z = z.contiguous()
+    if k < 2 or kc < k or z.numel() % kc:
+        raise ValueError(f"bad class padding: k={k}, kc={kc}, {z.numel()} margins")
+    n = z.numel() // kc
+    dev = z.device
+    labels = labels.to(device=dev, dtype=torch.float32).contiguous()
+    sw = _prep_weights(sample_weight, dev)
+    if labels.numel() != n or (sw is not None and sw.numel() != n):
+        raise ValueError("labels / sample_weight must match margins [n]")
+    ints = torch.zeros(k * k + 2, dtype=torch.int64, device=dev)
+    sums = torch.zeros(2, dtype=torch.float64, device=dev)
+    cnt_ws, red_ws = _metrics_ws(dev)
+    rc = lib.agd_multiclass_metrics(
+        _ptr(z), _ptr(labels), _ptr(sw), n, k, kc, _ptr(ints), _ptr(sums),
+        _ptr(cnt_ws), _ptr(red_ws), _stream(z))
+    _check(rc)
+    return (ints[:k * k].reshape(k, k), sums, ints[k * k],
+            _min_weight(ints[k * k + 1], sw is not None, n))

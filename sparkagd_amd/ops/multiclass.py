@@ -400,3 +400,17 @@ def grad_from_mult_multi(features, m_padded_flat, k):
     acc = torch.float32 if features.dtype in (torch.bfloat16, torch.float16) else features.dtype
     m = m_padded_flat.reshape(n, kc)[:, :k].to(acc)
     return (features.to(acc).T @ m).reshape(-1)
+
+
+def multiclass_metrics(margins_padded_flat, labels, k, sample_weight=None):
+    """(conf i64 [k, k], sums f64 [2], bad_labels, min_weight) from padded
+    margins — one fused pass on GPU (k_multiclass_metrics), the oracle
+    ``reference.multiclass_metrics`` on CPU."""
+    kc = padded_k(k)
+    if _use_hip(margins_padded_flat):
+        from . import hiplib
+
+        return hiplib.multiclass_metrics(margins_padded_flat, labels, k, kc,
+                                         sample_weight)
+    return _ref.multiclass_metrics(margins_padded_flat, labels, k, kc,
+                                   sample_weight)

@@ -386,3 +386,129 @@ def csc_scale_vals(colptr: torch.Tensor, val: torch.Tensor, scale: torch.Tensor,
         return res
     out.copy_(res)
     return out
+
+
+# --- evaluation metrics (oracles of k_binary_metrics / k_multiclass_metrics) ---
+
+METRICS_MAX_BINS = 4096
+METRICS_FIXED_ONE = 2 ** 32  # a weighted example counts llrint(w * 2^32) units
+
+
+def stable_softplus(t: torch.Tensor) -> torch.Tensor:
+    """log(1 + e^t) as t + log1p(e^-t) for t > 0 and log1p(e^t) otherwise:
+    exact to rounding for every t, 0 at -inf and +inf at +inf (the form the
+    HIP kernels use; ``torch.nn.functional.softplus`` switches to the
+    identity above 20 and so differs by up to 2e-9 there)."""
+    return torch.where(t > 0, t + torch.log1p(torch.exp(-t)),
+                       torch.log1p(torch.exp(t)))
+
+
+def _metric_weights(sample_weight: Optional[torch.Tensor], n: int, device):
+    """(integer units [n] i64, weights [n] f64, min weight f32 0-dim)."""
+    if sample_weight is None:
+        return (torch.ones(n, dtype=torch.int64, device=device),
+                torch.ones(n, dtype=torch.float64, device=device),
+                torch.tensor(float("inf"), dtype=torch.float32, device=device))
+    w32 = sample_weight.to(device=device, dtype=torch.float32)
+    w = w32.to(torch.float64)
+    units = (w * METRICS_FIXED_ONE).round().to(torch.int64)
+    wmin = (w32.min() if n > 0 else
+            torch.tensor(float("inf"), dtype=torch.float32, device=device))
+    return units, w, wmin
+
+
+def binary_metrics(margins: torch.Tensor, labels: torch.Tensor,
+                   edges: torch.Tensor, cut: float,
+                   sample_weight: Optional[torch.Tensor] = None):
+    """Every sufficient statistic of the binary / regression metrics in one
+    pass over ``margins`` [n] (f32 or f64), ``labels`` [n] and optional
+    ``sample_weight`` [n] (f32):
+
+    * ``hist_pos``, ``hist_neg`` int64 [B], B = len(edges) + 1: the bin of z
+      is the number of edges <= z (``torch.bucketize(right=True)``; ``edges``
+      strictly increasing, in the margins' dtype); an example is positive
+      when y > 0.5 and adds 1, or ``round(w * 2^32)`` when weighted;
+    * ``conf`` int64 [4] = (tp, fp, fn, tn) for the prediction ``z > cut``
+      (``cut`` rounded to the margins' dtype), same units;
+    * ``sums`` f64 [7] = Σw, Σw·logloss(z, y), Σw·(z−y)², Σw·|z−y|, Σw·y,
+      Σw·y², Σw·(z−y), each term evaluated in f64 from the stored margin,
+      the log-loss through :func:`stable_softplus`;
+    * ``nan_count`` int64 0-dim: NaN margins, which enter nothing else;
+    * ``min_weight`` f32 0-dim (+inf when unweighted).
+    """
+    if margins.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"margins must be f32 or f64, got {margins.dtype}")
+    z = margins.reshape(-1)
+    n = z.numel()
+    dev = z.device
+    edges = edges.to(device=dev, dtype=z.dtype).reshape(-1)
+    nbins = edges.numel() + 1
+    if nbins > METRICS_MAX_BINS:
+        raise ValueError(f"at most {METRICS_MAX_BINS} bins, got {nbins}")
+    units, w, wmin = _metric_weights(sample_weight, n, dev)
+    keep = ~torch.isnan(z)
+    nan_count = (~keep).sum().to(torch.int64)
+    z, y = z[keep], labels.to(dev).reshape(-1)[keep]
+    units, w = units[keep], w[keep]
+    pos = y > 0.5
+    if nbins > 1:
+        bins = torch.bucketize(z, edges, right=True)
+    else:
+        bins = torch.zeros(z.numel(), dtype=torch.int64, device=dev)
+    zero = torch.zeros(nbins, dtype=torch.int64, device=dev)
+    hist_pos = zero.clone().index_add_(0, bins[pos], units[pos])
+    hist_neg = zero.clone().index_add_(0, bins[~pos], units[~pos])
+    pred = z > torch.tensor(cut, dtype=z.dtype, device=dev)
+    conf = torch.stack([units[pos & pred].sum(), units[~pos & pred].sum(),
+                        units[pos & ~pred].sum(), units[~pos & ~pred].sum()])
+    zd, yd = z.to(torch.float64), y.to(torch.float64)
+    logloss = torch.where(pos, stable_softplus(-zd), stable_softplus(zd))
+    diff = zd - yd
+    sums = torch.stack([w.sum(), (w * logloss).sum(), (w * (diff * diff)).sum(),
+                        (w * diff.abs()).sum(), (w * yd).sum(),
+                        (w * (yd * yd)).sum(), (w * diff).sum()])
+    return hist_pos, hist_neg, conf, sums, nan_count, wmin
+
+
+def argmax_lowest(z: torch.Tensor) -> torch.Tensor:
+    """Row argmax of z [n, K] with the LOWEST index winning ties (spelled
+    out: ``torch.argmax`` leaves the tie rule unspecified)."""
+    k = z.shape[1]
+    idx = torch.arange(k, device=z.device).expand_as(z)
+    is_max = z == z.max(dim=1, keepdim=True).values
+    return torch.where(is_max, idx, torch.full_like(idx, k)).min(dim=1).values
+
+
+def multiclass_metrics(margins_padded_flat: torch.Tensor, labels: torch.Tensor,
+                       k: int, kc: int,
+                       sample_weight: Optional[torch.Tensor] = None):
+    """Sufficient statistics of the multiclass metrics from padded margins
+    [n * kc] (what ``MultinomialLogisticGradient.margins`` returns),
+    restricted to the logical ``k`` classes:
+
+    * ``conf`` int64 [k, k], rows = true class, columns = argmax (lowest
+      index on ties), in the units of :func:`binary_metrics`;
+    * ``sums`` f64 [2] = Σw, Σw·(logsumexp(z) − z_y), the per-row loss
+      max-subtracted in the margins' dtype, accumulated in f64;
+    * ``bad_labels`` int64 0-dim: labels outside [0, k), left out of ``conf``;
+    * ``min_weight`` f32 0-dim (+inf when unweighted).
+    """
+    n = margins_padded_flat.numel() // kc
+    dev = margins_padded_flat.device
+    z = margins_padded_flat.reshape(n, kc)[:, :k]
+    units, w, wmin = _metric_weights(sample_weight, n, dev)
+    y = labels.to(dev).reshape(-1).to(torch.int64)
+    valid = (y >= 0) & (y < k)
+    bad = (~valid).sum().to(torch.int64)
+    pred = argmax_lowest(z)
+    yc = y.clamp(0, k - 1)
+    zy = torch.where(valid, z.gather(1, yc.unsqueeze(1)).squeeze(1),
+                     torch.zeros(n, dtype=z.dtype, device=dev))
+    # logsumexp(z) - z_y with the maximum taken out of BOTH terms: a confident
+    # correct row (z_y = max) then loses nothing to cancellation in f32
+    zmax = z.max(dim=1).values
+    loss = torch.log(torch.exp(z - zmax.unsqueeze(1)).sum(dim=1)) + (zmax - zy)
+    conf = torch.zeros(k * k, dtype=torch.int64, device=dev).index_add_(
+        0, (yc * k + pred)[valid], units[valid]).reshape(k, k)
+    sums = torch.stack([w.sum(), (w * loss.to(torch.float64)).sum()])
+    return conf, sums, bad, wmin
