@@ -31,8 +31,10 @@ from .models.updater import (
     L1Updater,
     SquaredL2Updater,
     ElasticNetUpdater,
+    FreeTailUpdater,
 )
-from .data import (DenseShard, CSRShard, MixedShard, generate_logistic_data,
+from .data import (DenseShard, CSRShard, MixedShard, InterceptShard,
+                   generate_logistic_data,
                    generate_dense_problem, generate_multiclass_problem)
 from .models.trainers import (LogisticRegressionWithAGD, LinearRegressionWithAGD,
                               SVMWithAGD, LogisticRegressionWithSGD,
@@ -65,6 +67,7 @@ __all__ = [
     "L1Updater",
     "SquaredL2Updater",
     "ElasticNetUpdater",
+    "FreeTailUpdater",
     "LogisticRegressionWithAGD",
     "LinearRegressionWithAGD",
     "SVMWithAGD",
@@ -80,6 +83,7 @@ __all__ = [
     "DenseShard",
     "CSRShard",
     "MixedShard",
+    "InterceptShard",
     "generate_logistic_data",
     "generate_dense_problem",
     "generate_multiclass_problem",

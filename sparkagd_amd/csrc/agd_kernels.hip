@@ -3139,3 +3139,286 @@ extern "C" int agd_multiclass_metrics(const void* Z, const void* labels,
   HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Native unpenalised intercept (weights laid out [w (d); b (1)], bias last).
+//
+// The extended operator is Ã = [A, 1]:  Ã·[w; b] = A·w + b  and
+// Ãᵀ·m = [Aᵀ·m; Σm], so the n·d shard stream is untouched (it keeps its
+// aligned 16-byte lane loads) and the intercept lives entirely in n-length
+// vector kernels. The bias is always read on the device from the weight
+// vector (src[idx]): it never becomes a host value or a kernel argument, so
+// an intercept run adds no host synchronisation and no host->device copy.
+// ---------------------------------------------------------------------------
+
+// k_multiplier for one margins array plus a third accumulator Σ mult[i] over
+// the values actually stored (m·sw when weighted, 0 for masked rows): the
+// gradient of the bias. red_part holds 3 doubles per block.
+template <typename TACC>
+__global__ __launch_bounds__(BLOCK) void k_multiplier_sum(
+    const TACC* __restrict__ margins, const float* __restrict__ labels,
+    const unsigned char* __restrict__ mask,
+    const float* __restrict__ sample_weight, int loss_type, ll n,
+    TACC* __restrict__ mult, double* __restrict__ red_part) {
+  double lsum = 0.0, cnt = 0.0, msum = 0.0;
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll i = (ll)blockIdx.x * BLOCK + threadIdx.x; i < n; i += stride) {
+    if (mask && !mask[i]) {
+      mult[i] = (TACC)0;
+      continue;
+    }
+    const TACC z = margins[i];
+    const TACC y = (TACC)labels[i];
+    TACC m, l;
+    loss_mult<TACC>(loss_type, z, y, m, l);
+    if (sample_weight) {
+      const TACC sw = (TACC)sample_weight[i];
+      const TACC ms = m * sw;
+      mult[i] = ms;
+      msum += (double)ms;
+      lsum += (double)l * (double)sw;
+      cnt += (double)sw;
+    } else {
+      mult[i] = m;
+      msum += (double)m;
+      lsum += (double)l;
+      cnt += 1.0;
+    }
+  }
+  double acc[3] = {lsum, cnt, msum};
+  block_reduce_partial<3>(acc, red_part);
+}
+
+// margins[i] += coef * src[idx]  (src: the device weight vector).
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_add_bias(T* __restrict__ margins,
+                                                    double coef,
+                                                    const T* __restrict__ src,
+                                                    ll idx, ll n) {
+  constexpr int VE = 16 / sizeof(T);
+  const T add = (T)coef * src[idx];
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const ll nv = n / VE;
+  for (ll i = gid; i < nv; i += stride) {
+    T mv[VE];
+    loadAcc<T, VE>(margins + i * VE, mv);
+#pragma unroll
+    for (int k = 0; k < VE; ++k) mv[k] += add;
+    storeAcc<T, VE>(margins + i * VE, mv);
+  }
+  const ll t = nv * VE + gid;  // tail (< VE elements)
+  if (t < n) margins[t] += add;
+}
+
+// k_at_margin_update with a constant term: with a free (unpenalised) last
+// coordinate the prox maps z = [z_w; z_b] to [pz·z_w + pg·g_w; z_b + pg·g_b],
+// and with zm = A·z_w + z_b, gm = A·g_w + g_b this gives
+//   zm' = pz·(zm − z_b) + pg·(gm − g_b) + z_b + pg·g_b
+//       = pz·zm + pg·gm + (1 − pz)·z_b,
+// i.e. zm' = pz·zm + pg·gm + c·src[idx] with c = 1 − pz, src = z_old.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_at_margin_update_off(
+    const T* __restrict__ zm_old, const T* __restrict__ xm_old,
+    const T* __restrict__ gm, double pz, double pg, double theta, double coef,
+    const T* __restrict__ src, ll idx, ll n, T* __restrict__ zm_new,
+    T* __restrict__ xm_new) {
+  constexpr int VE = 16 / sizeof(T);
+  const T tpz = (T)pz, tpg = (T)pg, tth = (T)theta, tom = (T)(1.0 - theta);
+  const T off = (T)coef * src[idx];
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const ll nv = n / VE;
+  for (ll i = gid; i < nv; i += stride) {
+    T zo[VE], xo[VE], gv[VE], zn[VE], xn[VE];
+    loadAcc<T, VE>(zm_old + i * VE, zo);
+    loadAcc<T, VE>(xm_old + i * VE, xo);
+    loadAcc<T, VE>(gm + i * VE, gv);
+#pragma unroll
+    for (int k = 0; k < VE; ++k) {
+      zn[k] = tpz * zo[k] + tpg * gv[k] + off;
+      xn[k] = tom * xo[k] + tth * zn[k];
+    }
+    storeAcc<T, VE>(zm_new + i * VE, zn);
+    storeAcc<T, VE>(xm_new + i * VE, xn);
+  }
+  const ll t = nv * VE + gid;  // tail (< VE elements)
+  if (t < n) {
+    const T z = tpz * zm_old[t] + tpg * gm[t] + off;
+    zm_new[t] = z;
+    xm_new[t] = tom * xm_old[t] + tth * z;
+  }
+}
+
+// k_prox whose last n_free coordinates take the plain step w − step·g
+// whatever the kind, and add nothing to the regularisation value. The first
+// free coordinate n − n_free may sit in the vector body or in the tail, so
+// both test the element index.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_prox_free(
+    int kind, const T* __restrict__ w, const T* __restrict__ g, double step,
+    double lam, double lam2, T* __restrict__ out,
+    double* __restrict__ reg_part, ll n, ll n_free) {
+  constexpr int VE = 16 / sizeof(T);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const T ts = (T)step, tl = (T)lam, tl2 = (T)lam2;
+  const ll n_reg = n - n_free;  // coordinates [0, n_reg) are regularised
+  double racc = 0.0;
+  const ll nv = n / VE;
+  for (ll i = gid; i < nv; i += stride) {
+    T wv[VE], gv[VE], ov[VE];
+    loadAcc<T, VE>(w + i * VE, wv);
+    loadAcc<T, VE>(g + i * VE, gv);
+#pragma unroll
+    for (int k = 0; k < VE; ++k)
+      ov[k] = (i * VE + k < n_reg)
+                  ? prox_elem(kind, wv[k], gv[k], ts, tl, tl2, racc)
+                  : wv[k] - ts * gv[k];
+    storeAcc<T, VE>(out + i * VE, ov);
+  }
+  const ll t = nv * VE + gid;
+  if (t < n)
+    out[t] = (t < n_reg) ? prox_elem(kind, w[t], g[t], ts, tl, tl2, racc)
+                         : w[t] - ts * g[t];
+  if (kind != PROX_SIMPLE) {
+    double acc[1] = {racc};
+    block_reduce_partial<1>(acc, reg_part);
+  }
+}
+
+// mult + {loss, count, Σmult} from one margins array. out (double[3]) must be
+// zeroed by the caller; dtype: 1 = f32, 2 = f64 (margins and mult).
+extern "C" int agd_multiplier_sum(const void* margins, const void* labels,
+                                  const void* mask, const void* sample_weight,
+                                  int loss_type, long long n, int dtype,
+                                  void* mult, void* out, void* red_ws,
+                                  void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = grid_for(n, BLOCK);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_multiplier_sum<float>), dim3(grid), dim3(BLOCK), 0,
+                       s, (const float*)margins, (const float*)labels,
+                       (const unsigned char*)mask, (const float*)sample_weight,
+                       loss_type, n, (float*)mult, (double*)red_ws);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_multiplier_sum<double>), dim3(grid), dim3(BLOCK), 0,
+                       s, (const double*)margins, (const float*)labels,
+                       (const unsigned char*)mask, (const float*)sample_weight,
+                       loss_type, n, (double*)mult, (double*)red_ws);
+  else {
+    snprintf(g_err, sizeof(g_err), "agd_multiplier_sum: bad dtype %d", dtype);
+    return 2;
+  }
+  hipLaunchKernelGGL((k_reduce_partials<3>), dim3(1), dim3(BLOCK), 0, s,
+                     (double*)red_ws, grid, (double*)out);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// In place: margins[i] += coef * src[idx], 0 <= idx < len(src) checked by
+// the caller.
+extern "C" int agd_add_bias(void* margins, double coef, const void* src,
+                            long long idx, long long n, int dtype,
+                            void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = grid_for(n, BLOCK * 4);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_add_bias<float>), dim3(grid), dim3(BLOCK), 0, s,
+                       (float*)margins, coef, (const float*)src, idx, n);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_add_bias<double>), dim3(grid), dim3(BLOCK), 0, s,
+                       (double*)margins, coef, (const double*)src, idx, n);
+  else {
+    snprintf(g_err, sizeof(g_err), "agd_add_bias: bad dtype %d", dtype);
+    return 2;
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+extern "C" int agd_at_margin_update_off(const void* zm_old, const void* xm_old,
+                                        const void* gm, double pz, double pg,
+                                        double theta, double coef,
+                                        const void* src, long long idx,
+                                        long long n, int dtype, void* zm_new,
+                                        void* xm_new, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = grid_for(n / (dtype == 2 ? 2 : 4) + 1, BLOCK);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_at_margin_update_off<float>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const float*)zm_old,
+                       (const float*)xm_old, (const float*)gm, pz, pg, theta,
+                       coef, (const float*)src, idx, n, (float*)zm_new,
+                       (float*)xm_new);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_at_margin_update_off<double>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const double*)zm_old,
+                       (const double*)xm_old, (const double*)gm, pz, pg, theta,
+                       coef, (const double*)src, idx, n, (double*)zm_new,
+                       (double*)xm_new);
+  else {
+    snprintf(g_err, sizeof(g_err), "at_margin_update_off: bad dtype %d", dtype);
+    return 2;
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// reg (double[1]) must be zeroed by the caller.
+extern "C" int agd_prox_free(int kind, const void* w, const void* g,
+                             double step, double lam, double lam2, void* out,
+                             void* reg, long long n, long long n_free,
+                             int dtype, void* red_ws, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_free < 0 || n_free > n) {
+    snprintf(g_err, sizeof(g_err), "agd_prox_free: n_free %lld outside [0, %lld]",
+             n_free, n);
+    return 2;
+  }
+  const int grid = grid_for(n, BLOCK * 4);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_prox_free<float>), dim3(grid), dim3(BLOCK), 0, s,
+                       kind, (const float*)w, (const float*)g, step, lam, lam2,
+                       (float*)out, (double*)red_ws, n, (ll)n_free);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_prox_free<double>), dim3(grid), dim3(BLOCK), 0, s,
+                       kind, (const double*)w, (const double*)g, step, lam,
+                       lam2, (double*)out, (double*)red_ws, n, (ll)n_free);
+  else {
+    snprintf(g_err, sizeof(g_err), "agd_prox_free: bad dtype %d", dtype);
+    return 2;
+  }
+  if (kind != PROX_SIMPLE)
+    hipLaunchKernelGGL((k_reduce_partials<1>), dim3(1), dim3(BLOCK), 0, s,
+                       (double*)red_ws, grid, (double*)reg);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// Aᵀ·mult for a CSR shard from a caller-supplied multiplier (the CSR twin of
+// agd_dense_eval mode 3). With a CSC copy: the deterministic gather through
+// the skew-robust path (heavy_cols == nullptr / n_tasks == 0: every column
+// takes the thread-per-column gather), grad is overwritten. Without: the
+// atomic scatter over the CSR arrays, grad must be zeroed by the caller.
+extern "C" int agd_csr_grad_from_mult(
+    const void* rowptr, const void* col, const void* val, const void* mult,
+    long long n, long long d, void* grad, const void* csc_colptr,
+    const void* csc_row, const void* csc_val, int heavy_T,
+    const void* heavy_cols, const void* taskptr, const void* task_heavy_idx,
+    long long n_heavy, long long n_tasks, int S, void* partial,
+    const void* light_order, void* stream) {
+  if (csc_colptr != nullptr) {
+    if (n_tasks == 0) heavy_T = 2147483647;  // no split: all columns light
+    return agd_csc_grad_skew(csc_colptr, csc_row, csc_val, mult, d, heavy_T,
+                             heavy_cols, taskptr, task_heavy_idx, n_heavy,
+                             n_tasks, S, partial, light_order, grad, stream);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  const int grid = grid_for(n, WAVES_PER_BLOCK);
+  hipLaunchKernelGGL(k_csr_grad, dim3(grid), dim3(BLOCK), 0, s,
+                     (const int*)rowptr, (const int*)col, (const float*)val,
+                     (const float*)mult, n, (float*)grad);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}

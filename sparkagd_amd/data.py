@@ -85,6 +85,12 @@ class DenseShard:
                                            loss_type, mask, need_grad,
                                            self.sample_weight)
 
+    def grad_from_mult(self, mult: torch.Tensor) -> torch.Tensor:
+        """A^T @ mult [d] for a caller-supplied multiplier [n]."""
+        acc = (torch.float64 if self.features.dtype == torch.float64
+               else torch.float32)
+        return ops.dense_grad_from_mult(self.features, mult.to(acc))
+
 
 class CSRShard:
     """One rank's rows of a CSR sparse design matrix.
@@ -254,11 +260,104 @@ class CSRShard:
                                          sample_weight=self.sample_weight,
                                          csc_heavy=self.csc_heavy)
 
+    def grad_from_mult(self, mult: torch.Tensor) -> torch.Tensor:
+        """A^T @ mult [d] for a caller-supplied multiplier [n]: the CSC
+        gather on a deterministic shard, the atomic scatter otherwise."""
+        if self.val.dtype != torch.float64:
+            mult = mult.to(torch.float32)
+        return ops.csr_grad_from_mult(self.rowptr, self.col, self.val, mult,
+                                      self._d, csc=self.csc,
+                                      csc_heavy=self.csc_heavy)
+
+
+class InterceptShard:
+    """A shard of any resident kind with a native intercept: the operator
+    ``[A, 1]`` without the ones column ever being stored.
+
+    Weights are ``[w (d); b (1)]``, bias last (MLlib's ``appendBias``
+    layout), so ``d = inner.d + 1``. ``[A, 1]·[w; b] = A·w + b`` and
+    ``[A, 1]ᵀ·m = [Aᵀ·m; Σm]``: the inner shard's kernels stream its features
+    exactly as without an intercept (same dtype, same aligned row stride) and
+    the bias only touches n-length vectors. The bias is read on the device
+    from the weight vector, so no call synchronises with the host or copies
+    host->device. Binary losses only; pair it with
+    :class:`~sparkagd_amd.models.updater.FreeTailUpdater` so the bias is not
+    regularised.
+    """
+
+    kind = "intercept"
+
+    def __init__(self, inner):
+        k = getattr(inner, "kind", None)
+        if k == "dense_streamed":
+            raise NotImplementedError(
+                "InterceptShard cannot wrap a HostStreamedDenseShard: its "
+                "chunked evaluation has no multiplier-in entry point")
+        if k == "intercept":
+            raise ValueError("shard already has an intercept")
+        if not hasattr(inner, "grad_from_mult"):
+            raise TypeError(
+                f"InterceptShard needs a shard with grad_from_mult, got "
+                f"{type(inner).__name__}")
+        self.inner = inner
+
+    @property
+    def n(self) -> int:
+        return self.inner.n
+
+    @property
+    def d(self) -> int:
+        return self.inner.d + 1
+
+    @property
+    def device(self) -> torch.device:
+        return self.inner.device
+
+    @property
+    def labels(self) -> torch.Tensor:
+        return self.inner.labels
+
+    @property
+    def sample_weight(self) -> Optional[torch.Tensor]:
+        return getattr(self.inner, "sample_weight", None)
+
+    @property
+    def nbytes(self) -> int:
+        return self.inner.nbytes
+
+    def margins(self, v: torch.Tensor) -> torch.Tensor:
+        d = self.inner.d
+        if v.numel() != d + 1:
+            raise ValueError(f"expected [w; b] of length {d + 1}, got {v.numel()}")
+        m = self.inner.margins(v[:d])
+        return ops.add_bias_(m.contiguous(), 1.0, v, d)
+
+    def eval_from_margins(self, margins: torch.Tensor, loss_type: int,
+                          mask: Optional[torch.Tensor] = None,
+                          need_grad: bool = True):
+        mult, lc3 = ops.multiplier_loss_sum(margins, self.labels, loss_type,
+                                            mask, self.sample_weight)
+        loss_count = lc3[:2]
+        if not need_grad:
+            return None, loss_count
+        g = self.inner.grad_from_mult(mult)
+        # [A^T·m ; Σm], assembled on the device
+        return torch.cat([g, lc3[2:3].to(g.dtype)]), loss_count
+
+    def eval(self, w: torch.Tensor, loss_type: int,
+             mask: Optional[torch.Tensor] = None, need_grad: bool = True):
+        grad, loss_count = self.eval_from_margins(self.margins(w), loss_type,
+                                                  mask, need_grad)
+        if grad is not None and grad.dtype != w.dtype:
+            grad = grad.to(w.dtype)
+        return grad, loss_count
+
 
 def add_intercept(shard: DenseShard) -> DenseShard:
     """Return a new DenseShard with an all-ones intercept column prepended
     (the reference suite's manual pattern, ``Suite.scala:47-49``). Copies the
-    features (n x (d+1))."""
+    features (n x (d+1)). ``InterceptShard`` / the trainers' ``intercept=True``
+    carry an unpenalised intercept without the copy, on every shard kind."""
     ones = torch.ones((shard.n, 1), dtype=shard.features.dtype,
                       device=shard.features.device)
     return DenseShard(torch.cat([ones, shard.features], dim=1).contiguous(),
@@ -557,6 +656,15 @@ class MixedShard:
             if need_grad:
                 grad = g if grad is None else grad + g.to(grad.dtype)
         return grad, loss_count
+
+    def grad_from_mult(self, mult: torch.Tensor) -> torch.Tensor:
+        """A^T @ mult [d]: the parts' own gradients over their row ranges,
+        summed on device."""
+        grad = None
+        for p, m in zip(self.parts, self._split(mult)):
+            g = p.grad_from_mult(m)
+            grad = g if grad is None else grad + g.to(grad.dtype)
+        return grad
 
 
 def reindex_columns(shard: CSRShard):

@@ -59,6 +59,11 @@ from .parallel.comm import Communicator
 logger = logging.getLogger(__name__)
 
 
+_INTERCEPT_ERROR = (
+    "the Gram solver does not support InterceptShard (its kernel matrix has "
+    "no bias term); use solver='direct' for a model with an intercept")
+
+
 class GramOperator:
     """K = A_local · A_globalᵀ, built chunked; matvec via the margins kernel
     (K is just a dense f32/f64 'shard' whose feature dimension is n_global)."""
@@ -68,6 +73,8 @@ class GramOperator:
                  mem_budget_bytes: int = 64 << 30,
                  k_dtype: Optional[str] = None):
         t0 = time.perf_counter()
+        if getattr(shard, "kind", None) == "intercept":
+            raise ValueError(_INTERCEPT_ERROR)
         if k_dtype is None:  # env override for A/B runs (bench.py)
             import os
 
@@ -215,6 +222,8 @@ def run_gram(
     comm = comm or Communicator()
     if not getattr(updater, "AFFINE_PROX", False):
         raise ValueError("run_gram requires an affine prox updater (Simple/SquaredL2)")
+    if getattr(data, "kind", None) == "intercept":
+        raise ValueError(_INTERCEPT_ERROR)
     if getattr(data, "kind", None) != "dense":
         raise ValueError("run_gram requires a DenseShard")
     # Multiclass: margins/multipliers are padded [n*KC] flats; every piece of

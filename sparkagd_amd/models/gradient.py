@@ -132,9 +132,18 @@ class MultinomialLogisticGradient(Gradient):
             raise ValueError("num_classes must be >= 2")
         self.num_classes = int(num_classes)
 
+    @staticmethod
+    def _check_shard(shard):
+        if getattr(shard, "kind", None) == "intercept":
+            raise ValueError(
+                "InterceptShard carries one bias for the binary losses; "
+                "MultinomialLogisticGradient needs a bias per class, which "
+                "is not supported")
+
     def eval(self, shard, w, mask=None, need_grad=True):
         from ..ops import multiclass as mc
 
+        self._check_shard(shard)
         if getattr(shard, "kind", None) == "csr":
             return mc.eval_multi_csr(shard, w, self.num_classes, mask,
                                      need_grad, shard.sample_weight)
@@ -144,6 +153,7 @@ class MultinomialLogisticGradient(Gradient):
     def margins(self, shard, v):
         from ..ops import multiclass as mc
 
+        self._check_shard(shard)
         if getattr(shard, "kind", None) == "csr":
             return mc.csr_margins_multi(shard, v, self.num_classes)
         return mc.margins_multi(shard.features, v, self.num_classes)
@@ -151,6 +161,7 @@ class MultinomialLogisticGradient(Gradient):
     def eval_from_margins(self, shard, margins, mask=None, need_grad=True):
         from ..ops import multiclass as mc
 
+        self._check_shard(shard)
         if getattr(shard, "kind", None) == "csr":
             return mc.eval_multi_csr_from_margins(shard, margins,
                                                   self.num_classes, mask,

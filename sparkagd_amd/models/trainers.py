@@ -78,29 +78,70 @@ def _weights_for(shard, weights: torch.Tensor) -> torch.Tensor:
     return w.contiguous()
 
 
+def _with_intercept(data, updater: Updater, initial_weights, initial_intercept: float):
+    """``intercept=True`` plumbing shared by the trainers: the shard wrapped
+    in an ``InterceptShard``, the updater in a ``FreeTailUpdater`` and the
+    start vector extended to ``[w; b]``."""
+    from ..data import InterceptShard
+    from .updater import FreeTailUpdater
+
+    data = InterceptShard(data)
+    if not isinstance(updater, FreeTailUpdater):
+        updater = FreeTailUpdater(updater, 1)
+    elif updater.n_free != 1:
+        raise ValueError("intercept=True needs a FreeTailUpdater with n_free=1")
+    if initial_weights is not None:
+        if initial_weights.numel() != data.d - 1:
+            raise ValueError(
+                f"initial_weights must be [{data.d - 1}] (the intercept is "
+                "given by initial_intercept)")
+        bias = torch.full((1,), float(initial_intercept),
+                          dtype=initial_weights.dtype,
+                          device=initial_weights.device)
+        initial_weights = torch.cat([initial_weights.reshape(-1), bias])
+    elif initial_intercept != 0.0:
+        wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
+        initial_weights = torch.zeros(data.d, device=data.device, dtype=wdtype)
+        initial_weights[-1] = float(initial_intercept)
+    return data, updater, initial_weights
+
+
+def _split_intercept(w: torch.Tensor):
+    """``[w; b]`` -> (w [d] as its own tensor, b as a float)."""
+    return w[:-1].clone(), float(w[-1])
+
+
 class LinearModel:
-    """A fitted generalized linear model: weights [d] (+ loss history).
+    """A fitted generalized linear model: weights [d], an ``intercept``
+    (0.0 for a model trained without one) and the loss history.
     MLlib-style model persistence via ``save``/``load`` (safetensors)."""
 
-    def __init__(self, weights: torch.Tensor, loss_history, link: str):
+    def __init__(self, weights: torch.Tensor, loss_history, link: str,
+                 intercept: float = 0.0):
         self.weights = weights
         self.loss_history = list(loss_history)
         self.link = link
+        self.intercept = float(intercept)
 
     def save(self, path: str) -> None:
         _save_model(path, self.weights, {"kind": "linear", "link": self.link,
-                                         "loss_history": self.loss_history})
+                                         "loss_history": self.loss_history,
+                                         "intercept": self.intercept})
 
     @classmethod
     def load(cls, path: str, device=None) -> "LinearModel":
         w, meta = _load_model(path, device)
         if meta.get("kind") != "linear":
             raise ValueError(f"not a LinearModel checkpoint: {meta.get('kind')}")
-        return cls(w, meta.get("loss_history", []), meta["link"])
+        return cls(w, meta.get("loss_history", []), meta["link"],
+                   meta.get("intercept", 0.0))
 
     def margins(self, features: torch.Tensor) -> torch.Tensor:
         acc = torch.float32 if features.dtype in (torch.bfloat16, torch.float16) else features.dtype
-        return features.to(acc) @ self.weights.to(acc)
+        z = features.to(acc) @ self.weights.to(acc)
+        if self.intercept != 0.0:
+            z = z + self.intercept
+        return z
 
     def predict(self, features: torch.Tensor,
                 threshold: Optional[float] = 0.5) -> torch.Tensor:
@@ -137,8 +178,11 @@ class LinearModel:
         """Margins [n] of a whole shard of any kind (dense bf16 / f32 / f64 /
         fp8, CSR, mixed, host-streamed) through the shard's own
         ``margins`` kernels — the features are read in place, never copied
-        or widened."""
-        return shard.margins(_weights_for(shard, self.weights))
+        or widened. The model's ``intercept`` is added when it is not 0."""
+        z = shard.margins(_weights_for(shard, self.weights))
+        if self.intercept != 0.0:
+            z = z + self.intercept
+        return z
 
     def predict_shard(self, shard,
                       threshold: Optional[float] = 0.5) -> torch.Tensor:
@@ -169,8 +213,19 @@ class _GLMTrainer:
         checkpoint_every: int = 0,
         resume_from: Optional[str] = None,
         feature_scaling: Union[bool, str] = False,
+        intercept: bool = False,
+        initial_intercept: float = 0.0,
     ) -> LinearModel:
-        """Fit the model. ``feature_scaling`` (default ``False``: the data is
+        """Fit the model. ``intercept=True`` (MLlib's ``setIntercept``) also
+        fits a bias, returned as ``model.intercept``: it is carried natively
+        (:class:`~sparkagd_amd.data.InterceptShard`, no ones column, any
+        shard kind but host-streamed) and never regularised — ``updater``,
+        default or given, is wrapped in a
+        :class:`~sparkagd_amd.models.updater.FreeTailUpdater`.
+        ``initial_intercept`` is its starting value; ``initial_weights`` stay
+        ``[d]``.
+
+        ``feature_scaling`` (default ``False``: the data is
         used as is) standardises the columns first, as MLlib's GLM trainers
         do (``useFeatureScaling``): ``True`` fits a
         :class:`~sparkagd_amd.stats.StandardScaler`, trains on an
@@ -193,6 +248,9 @@ class _GLMTrainer:
         cfg.convergence_tol = convergence_tol
         if updater is None:
             updater = SquaredL2Updater() if reg_param > 0 else SimpleUpdater()
+        if intercept:
+            data, updater, initial_weights = _with_intercept(
+                data, updater, initial_weights, initial_intercept)
         opt = AcceleratedGradientDescent(cls.GRADIENT_CLS(), updater, cfg, comm)
         opt.checkpoint_path = checkpoint_path
         opt.checkpoint_every = checkpoint_every
@@ -201,9 +259,13 @@ class _GLMTrainer:
             wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
             initial_weights = torch.zeros(data.d, device=data.device, dtype=wdtype)
         w = opt.optimize(data, initial_weights)
+        bias = 0.0
+        if intercept:
+            # no centring in the scaler, so the bias needs no mapping
+            w, bias = _split_intercept(w)
         if scaler is not None:
             w = scaler.unscale_weights(w)
-        return LinearModel(w, opt.loss_history, cls.LINK)
+        return LinearModel(w, opt.loss_history, cls.LINK, bias)
 
 
 def regularization_path(
@@ -215,6 +277,7 @@ def regularization_path(
     solver: str = "auto",
     comm: Optional[Communicator] = None,
     warm_start: bool = True,
+    intercept: bool = False,
 ):
     """Solve an L2 regularization path (one model per lambda), reusing the
     Gram operator across solves when eligible — hyperparameter sweeps then
@@ -223,6 +286,10 @@ def regularization_path(
 
     solver: 'auto' uses the Gram solver for dense shards (falling back to
     direct if K exceeds the memory budget), 'direct'/'gram' force a path.
+
+    intercept: also fit an unregularised bias (``model.intercept``) at every
+    lambda, warm-started along the path like the weights. Binary losses and
+    the direct solver only ('auto' selects it; 'gram' raises).
     """
     from ..gram import GramOperator
     from ..optimizer import run
@@ -230,6 +297,15 @@ def regularization_path(
     gradient = gradient or LogisticGradient()
     updater = SquaredL2Updater()
     is_multi = getattr(gradient, "IS_MULTICLASS", False)
+    if intercept:
+        if is_multi:
+            raise ValueError("intercept=True supports the binary losses only")
+        if solver == "gram":
+            raise ValueError(
+                "intercept=True needs the direct solver (solver='auto' or "
+                "'direct')")
+        solver = "direct"
+        data, updater, _ = _with_intercept(data, updater, None, 0.0)
     link = {0: "logistic", 1: "identity", 2: "hinge", 3: "hinge"}.get(
         gradient.LOSS_TYPE, "logistic")
     comm = comm or Communicator()
@@ -258,6 +334,9 @@ def regularization_path(
         if is_multi:
             models.append(MultinomialModel(w.clone(), hist,
                                            gradient.num_classes))
+        elif intercept:
+            wd, bias = _split_intercept(w)
+            models.append(LinearModel(wd, hist, link, bias))
         else:
             models.append(LinearModel(w.clone(), hist, link))
     return models
@@ -385,12 +464,16 @@ class _SGDTrainer:
         comm: Optional[Communicator] = None,
         step_schedule: str = "sqrt",
         feature_scaling: Union[bool, str] = False,
+        intercept: bool = False,
+        initial_intercept: float = 0.0,
     ) -> LinearModel:
         """``feature_scaling``: ``False`` | ``True`` | ``"inplace"``, as in
         the AGD trainers (column standardisation before optimising; ``True``
         holds a scaled copy of the features during training; the regulariser
         acts on the scaled-space weights; returned weights and
-        ``initial_weights`` are in the original feature space)."""
+        ``initial_weights`` are in the original feature space).
+        ``intercept`` / ``initial_intercept``: a native, unregularised bias,
+        as in the AGD trainers."""
         from ..optimizer import GradientDescent
         from ..stats import scaled_training_data
 
@@ -399,6 +482,9 @@ class _SGDTrainer:
 
         if updater is None:
             updater = SquaredL2Updater() if reg_param > 0 else SimpleUpdater()
+        if intercept:
+            data, updater, initial_weights = _with_intercept(
+                data, updater, initial_weights, initial_intercept)
         opt = (GradientDescent(cls.GRADIENT_CLS(), updater, comm)
                .setStepSize(step_size).setNumIterations(num_iterations)
                .setRegParam(reg_param).setMiniBatchFraction(mini_batch_fraction)
@@ -407,9 +493,12 @@ class _SGDTrainer:
             wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
             initial_weights = torch.zeros(data.d, device=data.device, dtype=wdtype)
         w = opt.optimize(data, initial_weights)
+        bias = 0.0
+        if intercept:
+            w, bias = _split_intercept(w)
         if scaler is not None:
             w = scaler.unscale_weights(w)
-        return LinearModel(w, opt.loss_history, cls.LINK)
+        return LinearModel(w, opt.loss_history, cls.LINK, bias)
 
 
 class LogisticRegressionWithSGD(_SGDTrainer):

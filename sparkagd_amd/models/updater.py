@@ -126,3 +126,56 @@ class SquaredL2Updater(Updater):
 
     def prox_margin_coeffs(self, step, reg_param):
         return 1.0 - step * reg_param, -step
+
+
+class FreeTailUpdater(Updater):
+    """``base`` with the last ``n_free`` coordinates left unregularised: they
+    take the plain step ``w - step*g`` whatever ``base`` is and add nothing
+    to the regularisation value. With ``n_free=1`` this is the updater of an
+    unpenalised intercept stored last (``InterceptShard``).
+
+    ``AFFINE_PROX`` and ``prox_margin_coeffs`` come from ``base``: they
+    describe the regularised block, and the optimizer's tracked path adds the
+    free coordinate's margin correction itself (``n_free == 1`` only; other
+    tail lengths run untracked)."""
+
+    def __init__(self, base: Updater, n_free: int = 1):
+        if isinstance(base, FreeTailUpdater):
+            raise ValueError("base is already a FreeTailUpdater")
+        if n_free < 0:
+            raise ValueError("n_free must be >= 0")
+        self.base = base
+        self.n_free = int(n_free)
+        self.PROX_KIND = base.PROX_KIND
+        # Margin tracking needs the (pz, pg) form: the optimizer adds the free
+        # coordinate's correction to the fused update, and there is no such
+        # correction on the prox_margins fallback. A base without
+        # coefficients therefore runs untracked.
+        try:
+            base.prox_margin_coeffs(1.0, 0.0)
+            has_coeffs = True
+        except NotImplementedError:
+            has_coeffs = False
+        self.AFFINE_PROX = (bool(base.AFFINE_PROX) and has_coeffs
+                            and self.n_free <= 1)
+
+    def _lambdas(self, reg_param: float):
+        if isinstance(self.base, ElasticNetUpdater):
+            return (self.base.l1_ratio * reg_param,
+                    (1.0 - self.base.l1_ratio) * reg_param)
+        return reg_param, 0.0
+
+    def prox_margin_coeffs(self, step, reg_param):
+        return self.base.prox_margin_coeffs(step, reg_param)
+
+    def compute(self, weights_old, gradient, step_size, iter, reg_param):  # noqa: A002
+        this_step = step_size / math.sqrt(iter)
+        lam, lam2 = self._lambdas(reg_param)
+        return ops.prox(self.PROX_KIND, weights_old, gradient, this_step, lam,
+                        lam2, n_free=self.n_free)
+
+    def reg_value(self, weights, reg_param):
+        lam, lam2 = self._lambdas(reg_param)
+        _, reg = ops.prox(self.PROX_KIND, weights, torch.zeros_like(weights),
+                          0.0, lam, lam2, n_free=self.n_free)
+        return reg

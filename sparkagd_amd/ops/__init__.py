@@ -162,23 +162,71 @@ def csr_eval_from_margins(rowptr, col, val, margins, labels, loss_type,
                                            sample_weight)
 
 
-def at_margin_update(zm_old, xm_old, gm, pz: float, pg: float, theta: float):
+def at_margin_update(zm_old, xm_old, gm, pz: float, pg: float, theta: float,
+                     offset=None):
     """Fused AT margin update: zm' = pz*zm + pg*gm; xm' = (1-th)*xm + th*zm'
-    — one pass on GPU, the axpby composition on CPU (identical algebra)."""
+    — one pass on GPU, the axpby composition on CPU (identical algebra).
+
+    ``offset=(coef, src, idx)`` adds the constant ``coef * src[idx]`` to every
+    zm' (the margin correction of an unpenalised intercept, read from the
+    device vector ``src``); ``None`` is the plain update."""
+    if offset is None:
+        if _use_hip(zm_old):
+            return _get_hip().at_margin_update(zm_old, xm_old, gm, pz, pg, theta)
+        zm_new = pz * zm_old + pg * gm
+        xm_new = (1.0 - theta) * xm_old + theta * zm_new
+        return zm_new, xm_new
+    coef, src, idx = offset
     if _use_hip(zm_old):
-        return _get_hip().at_margin_update(zm_old, xm_old, gm, pz, pg, theta)
-    zm_new = pz * zm_old + pg * gm
+        return _get_hip().at_margin_update_off(zm_old, xm_old, gm, pz, pg,
+                                               theta, coef, src, idx)
+    zm_new = pz * zm_old + pg * gm + coef * src[idx].to(zm_old.dtype)
     xm_new = (1.0 - theta) * xm_old + theta * zm_new
     return zm_new, xm_new
 
 
 def prox(
     kind: int, w: torch.Tensor, g: torch.Tensor, step: float, lam: float,
-    lam2: float = 0.0,
+    lam2: float = 0.0, n_free: int = 0,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One proximal step + regularisation value. The last ``n_free``
+    coordinates (an unpenalised intercept) take the plain gradient step and
+    stay out of the regularisation value."""
+    if n_free == 0:
+        if _use_hip(w):
+            return _get_hip().prox(kind, w, g, step, lam, lam2)
+        return reference.prox(kind, w, g, step, lam, lam2)
     if _use_hip(w):
-        return _get_hip().prox(kind, w, g, step, lam, lam2)
-    return reference.prox(kind, w, g, step, lam, lam2)
+        return _get_hip().prox_free(kind, w, g, step, lam, lam2, n_free)
+    return reference.prox_free(kind, w, g, step, lam, lam2, n_free)
+
+
+def multiplier_loss_sum(margins, labels, loss_type, mask=None,
+                        sample_weight=None):
+    """(mult [n], f64[3] = {loss, count, Σmult}) from margins."""
+    if _use_hip(margins):
+        return _get_hip().multiplier_loss_sum(margins, labels, loss_type,
+                                              mask, sample_weight)
+    return reference.multiplier_loss_sum(margins, labels, loss_type, mask,
+                                         sample_weight)
+
+
+def add_bias_(margins: torch.Tensor, coef: float, src: torch.Tensor,
+              idx: int) -> torch.Tensor:
+    """In place ``margins += coef * src[idx]`` with ``src`` a vector on the
+    margins' device: the bias is never fetched to the host."""
+    if _use_hip(margins):
+        return _get_hip().add_bias_(margins, coef, src, idx)
+    return reference.add_bias_(margins, coef, src, idx)
+
+
+def csr_grad_from_mult(rowptr, col, val, mult, d: int, csc=None,
+                       csc_heavy=None) -> torch.Tensor:
+    """A^T @ mult for a CSR shard from a caller-supplied multiplier."""
+    if _use_hip(val):
+        return _get_hip().csr_grad_from_mult(rowptr, col, val, mult, d, csc,
+                                             csc_heavy)
+    return reference.csr_grad_from_mult(rowptr, col, val, mult, d)
 
 
 def axpby(
@@ -270,6 +318,10 @@ __all__ = [
     "dense_eval_from_margins",
     "csr_margins",
     "csr_eval_from_margins",
+    "csr_grad_from_mult",
+    "multiplier_loss_sum",
+    "add_bias_",
+    "at_margin_update",
     "prox",
     "axpby",
     "fused_scalars",

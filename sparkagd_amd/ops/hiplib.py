@@ -111,6 +111,18 @@ def load() -> ctypes.CDLL:
     lib.agd_binary_metrics.argtypes = [P, I, P, P, P, I, D, LL, P, P, P, P, P]
     lib.agd_multiclass_metrics.restype = I
     lib.agd_multiclass_metrics.argtypes = [P, P, P, LL, I, I, P, P, P, P, P]
+    lib.agd_multiplier_sum.restype = I
+    lib.agd_multiplier_sum.argtypes = [P, P, P, P, I, LL, I, P, P, P, P]
+    lib.agd_add_bias.restype = I
+    lib.agd_add_bias.argtypes = [P, D, P, LL, LL, I, P]
+    lib.agd_at_margin_update_off.restype = I
+    lib.agd_at_margin_update_off.argtypes = [P, P, P, D, D, D, D, P, LL, LL, I,
+                                             P, P, P]
+    lib.agd_prox_free.restype = I
+    lib.agd_prox_free.argtypes = [I, P, P, D, D, D, P, P, LL, LL, I, P, P]
+    lib.agd_csr_grad_from_mult.restype = I
+    lib.agd_csr_grad_from_mult.argtypes = [P, P, P, P, LL, LL, P, P, P, P, I,
+                                           P, P, P, LL, LL, I, P, P, P]
 
     _lib = lib
     return lib
@@ -764,6 +776,141 @@ def at_margin_update(zm_old: torch.Tensor, xm_old: torch.Tensor,
         _stream(zm_old))
     _check(rc)
     return zm_new, xm_new
+
+
+# ---------------------------------------------------------------------------
+# Native intercept (weights [w; b], bias last): n-space kernels only
+# ---------------------------------------------------------------------------
+
+def _bias_src(src: torch.Tensor, idx: int, like: torch.Tensor) -> torch.Tensor:
+    """The device vector a bias is read from, checked against the vector it
+    is applied to (same dtype and device, index in range)."""
+    if src.dtype != like.dtype or src.device != like.device:
+        raise TypeError(
+            f"bias source ({src.dtype}, {src.device}) must match the margins "
+            f"({like.dtype}, {like.device})")
+    if not 0 <= idx < src.numel():
+        raise IndexError(f"bias index {idx} outside [0, {src.numel()})")
+    return src.contiguous()
+
+
+def multiplier_loss_sum(
+    margins: torch.Tensor,
+    labels: torch.Tensor,
+    loss_type: int,
+    mask: Optional[torch.Tensor] = None,
+    sample_weight: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mult [n], f64[3] = {loss, count, Σmult}) from margins
+    (k_multiplier_sum): the multiplier stage plus the bias gradient."""
+    lib = load()
+    if margins.dtype not in _VEC_DTYPE:
+        raise TypeError(f"margins must be f32 or f64, got {margins.dtype}")
+    dev = margins.device
+    n = margins.numel()
+    labels = labels.contiguous()
+    if labels.dtype != torch.float32:
+        labels = labels.to(torch.float32)
+    mask = _prep_mask(mask, dev)
+    sw = _prep_weights(sample_weight, dev)
+    mult = torch.empty(n, dtype=margins.dtype, device=dev)
+    out = torch.zeros(3, dtype=torch.float64, device=dev)
+    rc = lib.agd_multiplier_sum(
+        _ptr(margins.contiguous()), _ptr(labels), _ptr(mask), _ptr(sw),
+        loss_type, n, _VEC_DTYPE[margins.dtype], _ptr(mult), _ptr(out),
+        _ptr(_red_ws(dev)), _stream(margins))
+    _check(rc)
+    return mult, out
+
+
+def add_bias_(margins: torch.Tensor, coef: float, src: torch.Tensor,
+              idx: int) -> torch.Tensor:
+    """In place margins += coef * src[idx], the bias read on the device."""
+    lib = load()
+    if not margins.is_contiguous():
+        raise ValueError("add_bias_ needs contiguous margins")
+    src = _bias_src(src, idx, margins)
+    rc = lib.agd_add_bias(_ptr(margins), float(coef), _ptr(src), idx,
+                          margins.numel(), _VEC_DTYPE[margins.dtype],
+                          _stream(margins))
+    _check(rc)
+    return margins
+
+
+def at_margin_update_off(zm_old: torch.Tensor, xm_old: torch.Tensor,
+                         gm: torch.Tensor, pz: float, pg: float, theta: float,
+                         coef: float, src: torch.Tensor, idx: int):
+    """at_margin_update with the constant term coef * src[idx] added to zm'
+    (k_at_margin_update_off)."""
+    lib = load()
+    src = _bias_src(src, idx, zm_old)
+    zm_new = torch.empty_like(zm_old)
+    xm_new = torch.empty_like(xm_old)
+    rc = lib.agd_at_margin_update_off(
+        _ptr(zm_old.contiguous()), _ptr(xm_old.contiguous()),
+        _ptr(gm.contiguous()), float(pz), float(pg), float(theta),
+        float(coef), _ptr(src), idx, zm_old.numel(),
+        _VEC_DTYPE[zm_old.dtype], _ptr(zm_new), _ptr(xm_new), _stream(zm_old))
+    _check(rc)
+    return zm_new, xm_new
+
+
+def prox_free(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
+              lam: float, lam2: float, n_free: int
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """prox whose last n_free coordinates take the plain gradient step and
+    stay out of the regularisation value (k_prox_free)."""
+    lib = load()
+    if not 0 <= n_free <= w.numel():
+        raise ValueError(f"n_free {n_free} outside [0, {w.numel()}]")
+    out = torch.empty_like(w)
+    reg = torch.zeros((), dtype=torch.float64, device=w.device)
+    rc = lib.agd_prox_free(kind, _ptr(w.contiguous()), _ptr(g.contiguous()),
+                           float(step), float(lam), float(lam2), _ptr(out),
+                           _ptr(reg), w.numel(), int(n_free),
+                           _VEC_DTYPE[w.dtype], _ptr(_red_ws(w.device)),
+                           _stream(w))
+    _check(rc)
+    return out, reg
+
+
+def csr_grad_from_mult(rowptr, col, val, mult: torch.Tensor, d: int,
+                       csc=None, csc_heavy: Optional[dict] = None
+                       ) -> torch.Tensor:
+    """A^T @ mult for a CSR shard: the deterministic CSC gather when ``csc``
+    is given (heavy columns through the shard's task split), the fp32 atomic
+    scatter otherwise."""
+    lib = load()
+    assert val.is_cuda and val.dtype == torch.float32
+    n = rowptr.numel() - 1
+    if mult.dtype != torch.float32 or mult.numel() != n:
+        raise TypeError("CSR multiplier must be float32 [n]")
+    rowptr, col = _csr_idx(rowptr, col)
+    dev = val.device
+    mult = mult.contiguous()
+    if csc is None:
+        grad = torch.zeros(d, dtype=torch.float32, device=dev)  # accumulated
+        rc = lib.agd_csr_grad_from_mult(
+            _ptr(rowptr), _ptr(col), _ptr(val.contiguous()), _ptr(mult), n, d,
+            _ptr(grad), None, None, None, 0, None, None, None, 0, 0, 1, None,
+            None, _stream(val))
+    else:
+        grad = torch.empty(d, dtype=torch.float32, device=dev)  # overwritten
+        cp, cr, cv = csc
+        h = csc_heavy
+        if h is not None and h["task_idx"].numel() > 0:
+            heavy = (int(h["heavy_T"]), _ptr(h["cols"]), _ptr(h["taskptr"]),
+                     _ptr(h["task_idx"]), h["cols"].numel(),
+                     h["task_idx"].numel(), int(h["S"]), _ptr(h["partial"]),
+                     _ptr(h.get("order")))
+        else:
+            heavy = (0, None, None, None, 0, 0, 1, None,
+                     _ptr(h.get("order")) if h is not None else None)
+        rc = lib.agd_csr_grad_from_mult(
+            _ptr(rowptr), _ptr(col), _ptr(val.contiguous()), _ptr(mult), n, d,
+            _ptr(grad), _ptr(cp), _ptr(cr), _ptr(cv), *heavy, _stream(val))
+    _check(rc)
+    return grad
 
 
 # ---------------------------------------------------------------------------

@@ -200,9 +200,12 @@ def dense_grad_from_mult(features: torch.Tensor, mult: torch.Tensor) -> torch.Te
 
 def csr_margins(rowptr, col, val, v: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
     n = rowptr.numel() - 1
+    # f64 values keep f64 margins (as csr_eval does); everything narrower
+    # accumulates in f32 like the kernels
+    acc = torch.float64 if val.dtype == torch.float64 else torch.float32
     a = torch.sparse_csr_tensor(rowptr.to(torch.int64), col.to(torch.int64),
-                                val.to(torch.float32), size=(n, v.numel()))
-    return a @ v.to(torch.float32)
+                                val.to(acc), size=(n, v.numel()))
+    return a @ v.to(acc)
 
 
 def csr_eval_from_margins(rowptr, col, val, margins, labels, loss_type,
@@ -258,6 +261,54 @@ def prox(
     else:
         raise ValueError(f"unknown prox kind {kind}")
     return w_new, reg
+
+
+def prox_free(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
+              lam: float, lam2: float, n_free: int
+              ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``prox`` whose last ``n_free`` coordinates take the plain step
+    ``w - step*g`` whatever ``kind`` is and add nothing to the regularisation
+    value (an unpenalised intercept stored last)."""
+    n = w.numel()
+    if not 0 <= n_free <= n:
+        raise ValueError(f"n_free {n_free} outside [0, {n}]")
+    k = n - n_free
+    head, reg = prox(kind, w[:k], g[:k], step, lam, lam2)
+    return torch.cat([head, w[k:] - step * g[k:]]), reg
+
+
+def multiplier_loss_sum(
+    margins: torch.Tensor,
+    labels: torch.Tensor,
+    loss_type: int,
+    mask: Optional[torch.Tensor] = None,
+    sample_weight: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(mult [n], f64[3] = {loss sum, count, sum of mult}) from margins; the
+    third entry is the gradient of an intercept (masked rows count 0,
+    weighted rows m*sw)."""
+    mult, loss = _multiplier_and_loss(margins, labels, loss_type)
+    mult, loss, count = _apply_mask_weight(mult, loss, mask, sample_weight,
+                                           margins.numel(), margins.device)
+    return mult, torch.stack([loss.to(torch.float64).sum(), count,
+                              mult.to(torch.float64).sum()])
+
+
+def add_bias_(margins: torch.Tensor, coef: float, src: torch.Tensor,
+              idx: int) -> torch.Tensor:
+    """In place margins += coef * src[idx]."""
+    margins.add_(src[idx].to(margins.dtype), alpha=coef)
+    return margins
+
+
+def csr_grad_from_mult(rowptr, col, val, mult: torch.Tensor, d: int
+                       ) -> torch.Tensor:
+    """A^T @ mult over a CSR shard (f64 for f64 values, else f32)."""
+    n = rowptr.numel() - 1
+    acc = torch.float64 if val.dtype == torch.float64 else torch.float32
+    a = torch.sparse_csr_tensor(rowptr.to(torch.int64), col.to(torch.int64),
+                                val.to(acc), size=(n, d))
+    return a.t() @ mult.to(acc)
 
 
 def axpby(a: float, x: torch.Tensor, b: float, y: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -267,8 +267,17 @@ def run(
                     # fused: zm' and xm' in one pass (k_at_margin_update) —
                     # one launch + one fewer read stream than the
                     # prox-margins + axpby pair; identical algebra
-                    zm, xm = ops.at_margin_update(zm_old, xm_old, gm,
-                                                  pz, pg, theta)
+                    if getattr(updater, "n_free", 0) == 1 and pz != 1.0:
+                        # unpenalised last coordinate (intercept): the prox
+                        # leaves z_b unshrunk, so with zm = A·z_w + z_b
+                        #   zm' = pz·zm + pg·gm + (1 - pz)·z_b
+                        # (z_b read on device from z_old)
+                        zm, xm = ops.at_margin_update(
+                            zm_old, xm_old, gm, pz, pg, theta,
+                            offset=(1.0 - pz, z_old, z_old.numel() - 1))
+                    else:
+                        zm, xm = ops.at_margin_update(zm_old, xm_old, gm,
+                                                      pz, pg, theta)
                 else:
                     zm = updater.prox_margins(zm_old, gm, step, reg_param)
                     xm = ops.axpby(1.0 - theta, xm_old, theta, zm)
