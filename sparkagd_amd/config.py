@@ -67,6 +67,10 @@ class AGDConfig:
     #: recompute tracked margins from the weight vectors every k iterations
     #: (0 = never; drift is at fp32 rounding level).
     margin_refresh_every: int = 0
+    #: stream GPU bf16 dense shards as a lossless 12-bit packed copy
+    #: (optimizer.run docstring): 'auto', True (whenever the format allows)
+    #: or False (never)
+    pack_dense: bool | str = "auto"
 
     # Numerical guard below which the simple backtracking test switches to the
     # alternate (cancellation-safe) test (reference ``AGD.scala:234-235,272-278``).
@@ -98,3 +102,5 @@ class AGDConfig:
             raise ValueError("loss_history_mode must be exact|backtrack|none")
         if self.solver not in ("direct", "gram"):
             raise ValueError("solver must be direct|gram")
+        if self.pack_dense not in ("auto", True, False):
+            raise ValueError("pack_dense must be 'auto', True or False")

@@ -191,6 +191,83 @@ __device__ __forceinline__ void loadW(const TA* __restrict__ p, TACC (&out)[W]) 
   }
 }
 
+// ---------------------------------------------------------------------------
+// 12-bit packed bf16 shard (lossless; see docs/KERNELS.md "Packed bf16 stream").
+//
+// A group of 8 adjacent bf16 elements of a row is 12 bytes: dwords 0/1 hold
+// the low bytes (e0|m6..m0) of elements 0-3 / 4-7, dword 2 holds eight 4-bit
+// codes s<<3|k (byte j: element j low nibble, element 4+j high nibble). k
+// indexes an 8-entry table of high-byte magnitudes (e7..e1) that travels as
+// two u32 kernel arguments. pk12 is the tag type of one such group, so the
+// stream kernels index a packed shard in groups exactly as they index a raw
+// one in elements. A row is padded to a multiple of 32 groups (384 B, the
+// least common multiple of the group and the 128-B line): every wave's
+// 768-B sweep then starts on a line, which measured +8 % (margins) and +5 %
+// (gradient) stream rate at d = 10^6 over the unpadded stride.
+// ---------------------------------------------------------------------------
+
+struct pk12 { unsigned int w[3]; };
+
+#define PK_ROW_ALIGN_GROUPS 32
+
+// Row stride of a packed shard, in groups.
+__host__ __device__ __forceinline__ ll pk_row_groups(ll d) {
+  return (((d >> 3) + PK_ROW_ALIGN_GROUPS - 1) / PK_ROW_ALIGN_GROUPS) *
+         PK_ROW_ALIGN_GROUPS;
+}
+
+template <typename TA> struct IsPacked { static constexpr bool value = false; };
+template <> struct IsPacked<pk12> { static constexpr bool value = true; };
+
+// Address of element (r, c) of a row-major [*, d] shard; c % 8 == 0 for the
+// packed layout.
+template <typename TA>
+__device__ __forceinline__ const TA* elem_at(const TA* __restrict__ A, ll r,
+                                             ll d, ll c) {
+  if constexpr (IsPacked<TA>::value) return A + r * pk_row_groups(d) + (c >> 3);
+  else return A + r * d + c;
+}
+
+// loadW for the packed tag: one 12-B load, 10 byte-permutes + 6 bit ops, and
+// the 8 decoded values are the bf16 values bit for bit (as f32).
+template <typename TACC, bool NT>
+__device__ __forceinline__ void loadW_pk(const pk12* __restrict__ p,
+                                         TACC (&out)[8], unsigned lut_lo,
+                                         unsigned lut_hi) {
+  typedef unsigned int u32x3
+      __attribute__((ext_vector_type(3), aligned(4)));
+  const u32x3 v = NT ? __builtin_nontemporal_load((const u32x3*)p)
+                     : *(const u32x3*)p;
+  const unsigned z = v[2];
+  const unsigned hA =
+      __builtin_amdgcn_perm(lut_hi, lut_lo, z & 0x07070707u) |
+      ((z & 0x08080808u) << 4);
+  const unsigned hB =
+      __builtin_amdgcn_perm(lut_hi, lut_lo, (z >> 4) & 0x07070707u) |
+      (z & 0x80808080u);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned sel = ((4u + i) << 24) | ((unsigned)i << 16) | 0x0c0cu;
+    union { unsigned int u; float f; } a, b;
+    a.u = __builtin_amdgcn_perm(hA, v[0], sel);
+    b.u = __builtin_amdgcn_perm(hB, v[1], sel);
+    out[i] = (TACC)a.f;
+    out[4 + i] = (TACC)b.f;
+  }
+}
+
+// Full-width stream load of either layout (lut_* unused for raw shards).
+template <typename TA, typename TACC, int W, bool NT>
+__device__ __forceinline__ void loadA(const TA* __restrict__ p, TACC (&out)[W],
+                                      unsigned lut_lo, unsigned lut_hi) {
+  if constexpr (IsPacked<TA>::value) {
+    static_assert(W == 8, "packed groups are 8 wide");
+    loadW_pk<TACC, NT>(p, out, lut_lo, lut_hi);
+  } else {
+    loadW<TA, TACC, W, NT>(p, out);
+  }
+}
+
 // Vector load of W accumulator-typed elements (16-B chunks; the address is
 // W-element aligned by construction in the margins kernel).
 template <typename TACC, int W>
@@ -261,8 +338,10 @@ __device__ __forceinline__ void storeAcc(TACC* __restrict__ p, const TACC (&v)[W
 template <typename TA, typename TACC, int W, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_dense_margins(
     const TA* __restrict__ A, const TACC* __restrict__ w, ll n, ll d,
-    ll slab_w, int n_slabs, TACC* __restrict__ part) {
+    ll slab_w, int n_slabs, TACC* __restrict__ part, unsigned lut_lo,
+    unsigned lut_hi) {
   constexpr int R = (sizeof(TA) == 1) ? MARGIN_ROWS_FP8 : MARGIN_ROWS;
+  constexpr bool PK = IsPacked<TA>::value;  // no column tails: d % 8 == 0
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + wid;
@@ -276,7 +355,6 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
     const int nr = (int)((r0 + R <= n) ? R : (n - r0));
     const ll c_lo = s * slab_w;
     const ll c_hi = (c_lo + slab_w < d) ? c_lo + slab_w : d;
-    const TA* __restrict__ row0 = A + r0 * d;
     TACC acc[R];
 #pragma unroll
     for (int j = 0; j < R; ++j) acc[j] = (TACC)0;
@@ -288,12 +366,13 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
 #pragma unroll
         for (int j = 0; j < R; ++j) {
           TACC v[W];
-          loadW<TA, TACC, W, NT>(row0 + (ll)j * d + c, v);
+          loadA<TA, TACC, W, NT>(elem_at<TA>(A, r0 + j, d, c), v, lut_lo,
+                                 lut_hi);
 #pragma unroll
           for (int k = 0; k < W; ++k) acc[j] += v[k] * wv[k];
         }
       }
-      if (c < c_hi) {
+      if constexpr (!PK) if (c < c_hi) {
 #pragma unroll
         for (int k = 0; k < W; ++k)
           if (c + k < c_hi) {
@@ -301,10 +380,20 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
 #pragma unroll
             for (int j = 0; j < R; ++j) {
               TACC v[1];
-              loadW<TA, TACC, 1>(row0 + (ll)j * d + c + k, v);
+              loadW<TA, TACC, 1>(elem_at<TA>(A, r0 + j, d, c + k), v);
               acc[j] += v[0] * wk;
             }
           }
+      }
+    } else if constexpr (PK) {  // tail row group: whole groups, same k order
+      for (c = c_lo + (ll)lane * W; c < c_hi; c += (ll)WAVE * W) {
+        for (int j = 0; j < nr; ++j) {
+          TACC v[W];
+          loadA<TA, TACC, W, false>(elem_at<TA>(A, r0 + j, d, c), v, lut_lo,
+                                    lut_hi);
+#pragma unroll
+          for (int k = 0; k < W; ++k) acc[j] += v[k] * w[c + k];
+        }
       }
     } else {  // tail row group (at most one per slab; plain W stride)
       for (c = c_lo + (ll)lane * W; c < c_hi; c += (ll)WAVE * W) {
@@ -314,7 +403,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
             const TACC wk = w[c + k];
             for (int j = 0; j < nr; ++j) {
               TACC v[1];
-              loadW<TA, TACC, 1>(row0 + (ll)j * d + c + k, v);
+              loadW<TA, TACC, 1>(elem_at<TA>(A, r0 + j, d, c + k), v);
               acc[j] += v[0] * wk;
             }
           }
@@ -583,7 +672,8 @@ __global__ __launch_bounds__(BLOCK) void k_gram_state_update(
 template <typename TA, typename TACC, int W, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_dense_grad(
     const TA* __restrict__ A, const TACC* __restrict__ mult, ll n, ll d,
-    ll n_rb, TACC* __restrict__ part) {
+    ll n_rb, TACC* __restrict__ part, unsigned lut_lo, unsigned lut_hi) {
+  constexpr bool PK = IsPacked<TA>::value;  // no column tails: d % 8 == 0
   const ll cols_per_block = (ll)BLOCK * W;
   const ll n_cs = (d + cols_per_block - 1) / cols_per_block;
   for (ll b = blockIdx.x; b < n_rb * n_cs; b += gridDim.x) {
@@ -599,13 +689,13 @@ __global__ __launch_bounds__(BLOCK) void k_dense_grad(
     for (ll r = r_lo; r < r_hi; ++r) {
       const TACC m = mult[r];
       if (m == (TACC)0) continue;  // wave-uniform skip
-      const TA* __restrict__ p = A + r * d + c0;
       if (full) {
         TACC v[W];
-        loadW<TA, TACC, W, NT>(p, v);
+        loadA<TA, TACC, W, NT>(elem_at<TA>(A, r, d, c0), v, lut_lo, lut_hi);
 #pragma unroll
         for (int k = 0; k < W; ++k) acc[k] += m * v[k];
-      } else {
+      } else if constexpr (!PK) {
+        const TA* __restrict__ p = A + r * d + c0;
 #pragma unroll
         for (int k = 0; k < W; ++k)
           if (c0 + k < d) {
@@ -1573,6 +1663,214 @@ __global__ __launch_bounds__(BLOCK) void k_dot_diff(
 }
 
 // ---------------------------------------------------------------------------
+// Packed bf16 shard: one-time passes and escape corrections.
+// ---------------------------------------------------------------------------
+
+// Histogram of the high-byte magnitude (bits 14..8) of every element: LDS
+// integer counters per block, one private 128-bin row of 64-bit counts per
+// block in part[gridDim.x][128] (summed by the caller; integer => exact and
+// deterministic). Real data puts almost every element into 3-4 bins, so each
+// bin has PK_HIST_COPIES counters, copy-minor ([bin][copy]: the copies of a
+// bin lie on different LDS banks) and picked by lane: 5x the rate of one
+// counter per bin on randn data (7.7 -> 1.5 ms at 4096 x 10^6). Requires
+// n_elems % 8 == 0 and a 16-B aligned base.
+#define PK_HIST_COPIES 32
+
+__global__ __launch_bounds__(BLOCK) void k_dense_pack_hist(
+    const ubf16* __restrict__ A, ll n_groups,
+    unsigned long long* __restrict__ part) {
+  __shared__ unsigned int bins[128 * PK_HIST_COPIES];
+  for (int i = threadIdx.x; i < 128 * PK_HIST_COPIES; i += BLOCK) bins[i] = 0u;
+  __syncthreads();
+  using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
+  const int copy = threadIdx.x & (PK_HIST_COPIES - 1);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll g = (ll)blockIdx.x * BLOCK + threadIdx.x; g < n_groups; g += stride) {
+    const u16x8 v = *(const u16x8*)(A + g * 8);
+#pragma unroll
+    for (int k = 0; k < 8; ++k)
+      atomicAdd(&bins[((v[k] >> 8) & 0x7f) * PK_HIST_COPIES + copy], 1u);
+  }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    unsigned long long t = 0;
+    for (int c = 0; c < PK_HIST_COPIES; ++c)
+      t += bins[threadIdx.x * PK_HIST_COPIES + c];
+    part[(ll)blockIdx.x * 128 + threadIdx.x] = t;
+  }
+}
+
+// Table slot of a high-byte magnitude, or -1 (escape).
+__device__ __forceinline__ int pk_slot(unsigned h, unsigned lut_lo,
+                                       unsigned lut_hi) {
+  int k = -1;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (((lut_lo >> (8 * j)) & 0xffu) == h) k = j;
+    if (((lut_hi >> (8 * j)) & 0xffu) == h) k = 4 + j;
+  }
+  return k;
+}
+
+// Encode: one block per row (grid-stride over rows), one thread per 8-element
+// group. An escape (high-byte magnitude not in the table) is stored as the
+// all-zero code, which decodes to +0.0f because table slot 0 is 0x00; the
+// row's escape count goes to esc_count[r] and the group's 8-bit escape mask
+// to flags[r * row_groups + g] (zero in the row padding), so that collecting
+// the escapes does not have to read the shard again.
+__global__ __launch_bounds__(BLOCK) void k_dense_pack_encode(
+    const ubf16* __restrict__ A, ll n, ll d, unsigned lut_lo, unsigned lut_hi,
+    pk12* __restrict__ P, int* __restrict__ esc_count,
+    unsigned char* __restrict__ flags) {
+  using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
+  typedef unsigned int u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+  __shared__ int wsum[WAVES_PER_BLOCK];
+  const ll gpr = d >> 3;
+  const ll gs = pk_row_groups(d);
+  for (ll r = blockIdx.x; r < n; r += gridDim.x) {
+    int esc = 0;
+    for (ll g = threadIdx.x; g < gs; g += BLOCK) {
+      if (g >= gpr) {  // row padding: zero groups
+        u32x3 o;
+        o[0] = o[1] = o[2] = 0u;
+        *(u32x3*)(P + r * gs + g) = o;
+        flags[r * gs + g] = 0;
+        continue;
+      }
+      const u16x8 v = *(const u16x8*)(A + r * d + g * 8);
+      unsigned lo[2] = {0u, 0u}, z = 0u, mask = 0u;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const unsigned u = v[k];
+        const int slot = pk_slot((u >> 8) & 0x7fu, lut_lo, lut_hi);
+        unsigned code = 0u, lowb = 0u;
+        if (slot >= 0) {
+          code = ((u >> 15) << 3) | (unsigned)slot;
+          lowb = u & 0xffu;
+        } else {
+          ++esc;
+          mask |= 1u << k;
+        }
+        lo[k >> 2] |= lowb << (8 * (k & 3));
+        z |= code << (8 * (k & 3) + 4 * (k >> 2));
+      }
+      u32x3 o;
+      o[0] = lo[0];
+      o[1] = lo[1];
+      o[2] = z;
+      *(u32x3*)(P + r * gs + g) = o;
+      flags[r * gs + g] = (unsigned char)mask;
+    }
+    esc = wave_reduce_sum(esc);
+    __syncthreads();  // wsum reuse across rows
+    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = esc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int t = 0;
+#pragma unroll
+      for (int i = 0; i < WAVES_PER_BLOCK; ++i) t += wsum[i];
+      esc_count[r] = t;
+    }
+  }
+}
+
+// Escape coordinates in row order from the encode pass's flags: one wave per
+// row, 256 groups per sweep (4 flag bytes per lane; the padded row stride is
+// a multiple of 32 groups, so the dword loads are aligned and in bounds). A
+// wave prefix sum places each lane's escapes after those of lower lanes, so
+// col[] ascends inside a row. rowptr is the exclusive scan of esc_count.
+__global__ __launch_bounds__(BLOCK) void k_dense_pack_escapes(
+    const ubf16* __restrict__ A, ll n, ll d,
+    const unsigned char* __restrict__ flags, const int* __restrict__ rowptr,
+    int* __restrict__ col, float* __restrict__ val) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / WAVE;
+  const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
+  const ll gs = pk_row_groups(d);
+  for (ll r = wave_gid; r < n; r += n_waves) {
+    int base = rowptr[r];
+    const int end = rowptr[r + 1];
+    if (base == end) continue;  // wave-uniform
+    for (ll g0 = 0; g0 < gs; g0 += 4 * WAVE) {
+      const ll g = g0 + 4 * lane;
+      unsigned mask = 0u;  // byte j: escape mask of group g + j
+      if (g < gs) mask = *(const unsigned int*)(flags + r * gs + g);
+      const int cnt = __popc(mask);
+      int incl = cnt;
+#pragma unroll
+      for (int off = 1; off < WAVE; off <<= 1) {
+        const int t = __shfl_up(incl, off, WAVE);
+        if (lane >= off) incl += t;
+      }
+      const int total = __shfl(incl, WAVE - 1, WAVE);
+      int pos = base + incl - cnt;
+      while (mask) {  // ascending bit = ascending column
+        const int b = __ffs((int)mask) - 1;
+        mask &= mask - 1u;
+        const ll c = g * 8 + b;
+        if (pos < end && c < d) {  // the bounds keep loads and stores inside
+          col[pos] = (int)c;
+          val[pos] = bf2f(A[r * d + c]);
+        }
+        ++pos;
+      }
+      base += total;
+    }
+  }
+}
+
+// margins[r] += sum_k val[k] * v[col[k]] over the row's escapes (one wave
+// per row; rows without escapes are left untouched).
+__global__ __launch_bounds__(BLOCK) void k_pack_fix_margins(
+    const int* __restrict__ rowptr, const int* __restrict__ col,
+    const float* __restrict__ val, const float* __restrict__ w, ll n,
+    float* __restrict__ margins) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / WAVE;
+  const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
+  for (ll r = wave_gid; r < n; r += n_waves) {
+    const int k_lo = rowptr[r], k_hi = rowptr[r + 1];
+    if (k_lo == k_hi) continue;
+    float acc = 0.f;
+    for (int k = k_lo + lane; k < k_hi; k += WAVE) acc += val[k] * w[col[k]];
+    acc = wave_reduce_sum(acc);
+    if (lane == 0) margins[r] += acc;
+  }
+}
+
+// grad[c] += sum_k val[k] * m[row[k]] over the column's escapes (one thread
+// per column, the k_csc_grad body). A zero multiplier contributes zero, as
+// the m == 0 row skip of the stream kernel does (inf * 0 never forms).
+__global__ __launch_bounds__(BLOCK) void k_pack_fix_grad(
+    const int* __restrict__ colptr, const int* __restrict__ row,
+    const float* __restrict__ val, const float* __restrict__ mult, ll d,
+    float* __restrict__ grad) {
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll c = (ll)blockIdx.x * BLOCK + threadIdx.x; c < d; c += stride) {
+    const int k_lo = colptr[c], k_hi = colptr[c + 1];
+    if (k_lo == k_hi) continue;
+    float acc = 0.f;
+    for (int k = k_lo; k < k_hi; ++k) {
+      const float m = mult[row[k]];
+      if (m != 0.f) acc += val[k] * m;
+    }
+    grad[c] += acc;
+  }
+}
+
+// Escape side lists + decode table of a packed shard (dense_eval_t).
+struct PackSide {
+  unsigned lut_lo, lut_hi;
+  const int* rowptr;  // CSR [n+1], col/val [nnz]
+  const int* col;
+  const float* val;
+  const int* colptr;  // CSC [d+1], row/cval [nnz]
+  const int* row;
+  const float* cval;
+  ll nnz;
+};
+
+// ---------------------------------------------------------------------------
 // Host API (C ABI). All pointers are DEVICE pointers; stream is a hipStream_t.
 // dtype codes: 0 = bf16, 1 = f32, 2 = f64 (features); vector ops: 1 = f32,
 // 2 = f64.
@@ -1657,14 +1955,23 @@ static int dense_eval_t(const void* A, const float* labels,
                         void* mult_ws, void* part_ws, ll n_rb, int loss_type,
                         int n_slabs, int need_grad, int margins_algo,
                         int nt_loads, int mode, double* red_ws,
-                        hipStream_t stream) {
+                        hipStream_t stream, const PackSide* pk = nullptr) {
   const TA* a = (const TA*)A;
+  const unsigned lut_lo = pk ? pk->lut_lo : 0u;
+  const unsigned lut_hi = pk ? pk->lut_hi : 0u;
   const TACC* wp = (const TACC*)w;
   TACC* margins = (TACC*)margins_ws;
   TACC* mult = (TACC*)mult_ws;
   TACC* grad = (TACC*)grad_out;
   TACC* part = (n_rb == 1) ? grad : (TACC*)part_ws;
-  const int algo = margins_algo_eff(margins_algo, sizeof(TA) == 2 ? 0 : (sizeof(TA) == 4 ? 1 : 2), d);
+  // features dtype code for the algorithm choice; a packed shard is bf16
+  // data that only the VALU kernel can decode
+  const int dcode = IsPacked<TA>::value ? 0
+                    : sizeof(TA) == 1   ? 3
+                    : sizeof(TA) == 2   ? 0
+                    : sizeof(TA) == 4   ? 1
+                                        : 2;
+  const int algo = IsPacked<TA>::value ? 1 : margins_algo_eff(margins_algo, dcode, d);
   const bool use_mfma = (algo == 2) && (sizeof(TA) == 2) && (W == 8);
 
   ll slab_w = d;
@@ -1691,11 +1998,20 @@ static int dense_eval_t(const void* A, const float* labels,
     if (nt_loads)
       hipLaunchKernelGGL((k_dense_margins<TA, TACC, W, true>), dim3(grid),
                          dim3(BLOCK), 0, stream, a, wp, n, d, slab_w, n_slabs,
-                         margins);
+                         margins, lut_lo, lut_hi);
     else
       hipLaunchKernelGGL((k_dense_margins<TA, TACC, W, false>), dim3(grid),
                          dim3(BLOCK), 0, stream, a, wp, n, d, slab_w, n_slabs,
-                         margins);
+                         margins, lut_lo, lut_hi);
+  }
+  if constexpr (IsPacked<TA>::value) {
+    // escapes: add their products onto slab 0 (the slab sum finishes them)
+    if (mode != 2 && mode != 3 && pk && pk->nnz > 0) {
+      const int grid = grid_for(n, WAVES_PER_BLOCK);
+      hipLaunchKernelGGL(k_pack_fix_margins, dim3(grid), dim3(BLOCK), 0, stream,
+                         pk->rowptr, pk->col, pk->val, (const float*)w, n,
+                         (float*)margins);
+    }
   }
   if (mode == 1) {  // margins only: reduce slabs in place and return
     if (n_slabs > 1) {
@@ -1721,15 +2037,25 @@ static int dense_eval_t(const void* A, const float* labels,
       const int grid = grid_for(n_rb * n_cs, 1);
       if (nt_loads)
         hipLaunchKernelGGL((k_dense_grad<TA, TACC, W, true>), dim3(grid),
-                           dim3(BLOCK), 0, stream, a, mult, n, d, n_rb, part);
+                           dim3(BLOCK), 0, stream, a, mult, n, d, n_rb, part,
+                           lut_lo, lut_hi);
       else
         hipLaunchKernelGGL((k_dense_grad<TA, TACC, W, false>), dim3(grid),
-                           dim3(BLOCK), 0, stream, a, mult, n, d, n_rb, part);
+                           dim3(BLOCK), 0, stream, a, mult, n, d, n_rb, part,
+                           lut_lo, lut_hi);
     }
     if (n_rb > 1) {
       const int grid = grid_for(d, BLOCK);
       hipLaunchKernelGGL((k_grad_reduce<TACC>), dim3(grid), dim3(BLOCK), 0,
                          stream, part, n_rb, d, grad);
+    }
+    if constexpr (IsPacked<TA>::value) {
+      if (pk && pk->nnz > 0) {
+        const int grid = grid_for(d, BLOCK);
+        hipLaunchKernelGGL(k_pack_fix_grad, dim3(grid), dim3(BLOCK), 0, stream,
+                           pk->colptr, pk->row, pk->cval, (const float*)mult,
+                           d, (float*)grad);
+      }
     }
   }
   HIP_CHECK(hipGetLastError());
@@ -1765,6 +2091,122 @@ extern "C" int agd_dense_eval(const void* A, int a_dtype, const void* labels,
   }
   snprintf(g_err, sizeof(g_err), "agd_dense_eval: bad dtype %d", a_dtype);
   return 2;
+}
+
+// --- Packed bf16 shard entry points ---------------------------------------
+
+static int pack_shape_ok(const char* who, const void* A, ll n, ll d) {
+  if (n < 1 || d < 8 || d % 8 != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: needs n >= 1 and d %% 8 == 0 (n=%lld d=%lld)",
+             who, n, d);
+    return 0;
+  }
+  if (((uintptr_t)A & 15) != 0) {
+    snprintf(g_err, sizeof(g_err), "%s: base pointer must be 16-byte aligned", who);
+    return 0;
+  }
+  return 1;
+}
+
+// Blocks (rows of 128 64-bit counts) agd_dense_pack_hist writes.
+extern "C" int agd_dense_pack_hist_blocks(long long n, long long d) {
+  return grid_for(n * (d / 8), (ll)BLOCK * 16);
+}
+
+extern "C" int agd_dense_pack_hist(const void* A, long long n, long long d,
+                                   void* part, void* stream) {
+  if (!pack_shape_ok("agd_dense_pack_hist", A, n, d)) return 2;
+  const int grid = agd_dense_pack_hist_blocks(n, d);
+  hipLaunchKernelGGL(k_dense_pack_hist, dim3(grid), dim3(BLOCK), 0,
+                     (hipStream_t)stream, (const ubf16*)A, n * (d / 8),
+                     (unsigned long long*)part);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+static int pack_lut_ok(const char* who, unsigned lut_lo) {
+  if ((lut_lo & 0xffu) != 0u) {
+    snprintf(g_err, sizeof(g_err), "%s: table slot 0 must be 0x00 (escapes decode to +0.0)", who);
+    return 0;
+  }
+  return 1;
+}
+
+// Bytes of one packed row (d/8 groups of 12 B, padded to 384 B).
+extern "C" long long agd_dense_pack_row_bytes(long long d) {
+  return pk_row_groups(d) * 12;
+}
+
+// packed [n, agd_dense_pack_row_bytes(d)] bytes; esc_count [n] int32;
+// flags [n, agd_dense_pack_row_bytes(d) / 12] bytes.
+extern "C" int agd_dense_pack_encode(const void* A, long long n, long long d,
+                                     unsigned lut_lo, unsigned lut_hi,
+                                     void* packed, void* esc_count,
+                                     void* flags, void* stream) {
+  if (!pack_shape_ok("agd_dense_pack_encode", A, n, d)) return 2;
+  if (!pack_lut_ok("agd_dense_pack_encode", lut_lo)) return 2;
+  const int grid = grid_for(n, 1);
+  hipLaunchKernelGGL(k_dense_pack_encode, dim3(grid), dim3(BLOCK), 0,
+                     (hipStream_t)stream, (const ubf16*)A, (ll)n, (ll)d, lut_lo,
+                     lut_hi, (pk12*)packed, (int*)esc_count,
+                     (unsigned char*)flags);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// rowptr [n+1] int32 = exclusive scan of esc_count; col/val sized rowptr[n].
+extern "C" int agd_dense_pack_escapes(const void* A, long long n, long long d,
+                                      const void* flags, const void* rowptr,
+                                      void* col, void* val, void* stream) {
+  if (!pack_shape_ok("agd_dense_pack_escapes", A, n, d)) return 2;
+  const int grid = grid_for(n, WAVES_PER_BLOCK);
+  hipLaunchKernelGGL(k_dense_pack_escapes, dim3(grid), dim3(BLOCK), 0,
+                     (hipStream_t)stream, (const ubf16*)A, (ll)n, (ll)d,
+                     (const unsigned char*)flags, (const int*)rowptr, (int*)col,
+                     (float*)val);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// agd_dense_eval (modes 0-3) on the packed copy of a bf16 shard: same
+// planning (agd_dense_rowblocks / agd_margin_slabs with a_dtype 0), same
+// workspaces, plus the decode table and the escape side lists (CSR for
+// A·v, CSC for A^T·m; ignored when nnz == 0).
+extern "C" int agd_dense_eval_packed(
+    const void* packed, unsigned lut_lo, unsigned lut_hi, const void* esc_rowptr,
+    const void* esc_col, const void* esc_val, const void* esc_colptr,
+    const void* esc_row, const void* esc_cval, long long esc_nnz,
+    const void* labels, const void* mask, const void* sample_weight,
+    const void* w, long long n, long long d, void* grad_out, void* loss_count,
+    void* margins_ws, void* mult_ws, void* part_ws, long long n_rb,
+    int loss_type, int n_slabs, int need_grad, int nt_loads, int mode,
+    void* red_ws, void* stream) {
+  if (!pack_shape_ok("agd_dense_eval_packed", packed, n, d)) return 2;
+  if (!pack_lut_ok("agd_dense_eval_packed", lut_lo)) return 2;
+  if (mode < 0 || mode > 3) {
+    snprintf(g_err, sizeof(g_err), "agd_dense_eval_packed: bad mode %d", mode);
+    return 2;
+  }
+  if (esc_nnz > 0 && (!esc_rowptr || !esc_col || !esc_val || !esc_colptr ||
+                      !esc_row || !esc_cval)) {
+    snprintf(g_err, sizeof(g_err), "agd_dense_eval_packed: escape lists missing (nnz=%lld)", esc_nnz);
+    return 2;
+  }
+  PackSide pk;
+  pk.lut_lo = lut_lo;
+  pk.lut_hi = lut_hi;
+  pk.rowptr = (const int*)esc_rowptr;
+  pk.col = (const int*)esc_col;
+  pk.val = (const float*)esc_val;
+  pk.colptr = (const int*)esc_colptr;
+  pk.row = (const int*)esc_row;
+  pk.cval = (const float*)esc_cval;
+  pk.nnz = esc_nnz;
+  return dense_eval_t<pk12, float, 8>(
+      packed, (const float*)labels, (const unsigned char*)mask,
+      (const float*)sample_weight, w, n, d, grad_out, (double*)loss_count,
+      margins_ws, mult_ws, part_ws, n_rb, loss_type, n_slabs, need_grad, 1,
+      nt_loads, mode, (double*)red_ws, (hipStream_t)stream, &pk);
 }
 
 // CSR applySmooth: margins -> multiplier/loss -> A^T·m.

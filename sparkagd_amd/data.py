@@ -52,6 +52,52 @@ class DenseShard:
                 raise ValueError("sample_weight must be [n]")
             self.sample_weight = sample_weight.to(
                 device=features.device, dtype=torch.float32).contiguous()
+        # cached 12-bit packed copy (packing.py) and the state of `features`
+        # it was built from
+        self._packed = None
+        self._packed_key = None
+        #: why the last pack() was refused (None after a successful one)
+        self.pack_refused: Optional[str] = None
+
+    def _features_key(self):
+        f = self.features
+        return (f.data_ptr(), tuple(f.shape), f.dtype, f._version)
+
+    def pack(self) -> bool:
+        """Build (or keep) the lossless 12-bit packed copy of a bf16 shard;
+        the GPU passes then stream it instead of `features`. Returns False,
+        with the reason in ``pack_refused``, when the shard cannot be packed
+        (not bf16, d % 8 != 0, too many escapes)."""
+        from . import packing
+
+        if self._packed_copy() is not None:
+            return True
+        pk, why = packing.pack_features(self.features)
+        self._packed, self.pack_refused = pk, why
+        self._packed_key = self._features_key() if pk is not None else None
+        return pk is not None
+
+    def unpack(self) -> None:
+        """Drop the packed copy (the shard streams `features` again)."""
+        self._packed = None
+        self._packed_key = None
+
+    def _packed_copy(self):
+        """The packed copy if it still matches `features`; an in-place
+        change of `features` (its version counter moved) drops it."""
+        if self._packed is not None and self._packed_key != self._features_key():
+            self.unpack()
+        return self._packed
+
+    @property
+    def is_packed(self) -> bool:
+        return self._packed_copy() is not None
+
+    def _packed_gpu(self):
+        pk = self._packed_copy()
+        if pk is not None and ops._use_hip(self.features):
+            return pk
+        return None
 
     @property
     def n(self) -> int:
@@ -71,16 +117,28 @@ class DenseShard:
 
     def eval(self, w: torch.Tensor, loss_type: int, mask: Optional[torch.Tensor] = None,
              need_grad: bool = True):
+        pk = self._packed_gpu()
+        if pk is not None:
+            return ops.dense_eval_packed(pk, self.labels, w, loss_type, mask,
+                                         need_grad, self.sample_weight)
         return ops.dense_eval(self.features, self.labels, w, loss_type, mask,
                               need_grad, self.sample_weight)
 
     # --- margin-state tracking support (one data pass instead of two when
     # the caller already holds A @ w; see optimizer.py 'track_margins') ---
     def margins(self, v: torch.Tensor) -> torch.Tensor:
+        pk = self._packed_gpu()
+        if pk is not None:
+            return ops.dense_margins_packed(pk, v)
         return ops.dense_margins(self.features, v)
 
     def eval_from_margins(self, margins: torch.Tensor, loss_type: int,
                           mask: Optional[torch.Tensor] = None, need_grad: bool = True):
+        pk = self._packed_gpu()
+        if pk is not None and need_grad:
+            return ops.dense_eval_from_margins_packed(
+                pk, margins, self.labels, loss_type, mask, need_grad,
+                self.sample_weight)
         return ops.dense_eval_from_margins(self.features, margins, self.labels,
                                            loss_type, mask, need_grad,
                                            self.sample_weight)
@@ -89,6 +147,9 @@ class DenseShard:
         """A^T @ mult [d] for a caller-supplied multiplier [n]."""
         acc = (torch.float64 if self.features.dtype == torch.float64
                else torch.float32)
+        pk = self._packed_gpu()
+        if pk is not None:
+            return ops.dense_grad_from_mult_packed(pk, mult.to(acc))
         return ops.dense_grad_from_mult(self.features, mult.to(acc))
 
 

@@ -111,6 +111,28 @@ def csr_eval(
                               need_grad, sample_weight)
 
 
+# Packed bf16 shards (packing.PackedDense): GPU only; DenseShard routes here
+# when it holds a valid packed copy.
+def dense_eval_packed(pk, labels, w, loss_type, mask=None, need_grad=True,
+                      sample_weight=None):
+    return _get_hip().dense_eval_packed(pk, labels, w, loss_type, mask,
+                                        need_grad, sample_weight)
+
+
+def dense_margins_packed(pk, v: torch.Tensor) -> torch.Tensor:
+    return _get_hip().dense_margins_packed(pk, v)
+
+
+def dense_eval_from_margins_packed(pk, margins, labels, loss_type, mask=None,
+                                   need_grad=True, sample_weight=None):
+    return _get_hip().dense_eval_from_margins_packed(
+        pk, margins, labels, loss_type, mask, need_grad, sample_weight)
+
+
+def dense_grad_from_mult_packed(pk, mult: torch.Tensor) -> torch.Tensor:
+    return _get_hip().dense_grad_from_mult_packed(pk, mult)
+
+
 def dense_margins(features: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     if _use_hip(features):
         return _get_hip().dense_margins(features, v)

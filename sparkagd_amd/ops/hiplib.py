@@ -56,6 +56,20 @@ def load() -> ctypes.CDLL:
     P, LL, I, D = ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int, ctypes.c_double
     lib.agd_dense_eval.restype = I
     lib.agd_dense_eval.argtypes = [P, I, P, P, P, P, LL, LL, P, P, P, P, P, LL, I, I, I, I, I, I, P, P]
+    U = ctypes.c_uint
+    lib.agd_dense_pack_hist_blocks.restype = I
+    lib.agd_dense_pack_hist_blocks.argtypes = [LL, LL]
+    lib.agd_dense_pack_hist.restype = I
+    lib.agd_dense_pack_hist.argtypes = [P, LL, LL, P, P]
+    lib.agd_dense_pack_encode.restype = I
+    lib.agd_dense_pack_encode.argtypes = [P, LL, LL, U, U, P, P, P, P]
+    lib.agd_dense_pack_escapes.restype = I
+    lib.agd_dense_pack_escapes.argtypes = [P, LL, LL, P, P, P, P, P]
+    lib.agd_dense_eval_packed.restype = I
+    lib.agd_dense_eval_packed.argtypes = [P, U, U, P, P, P, P, P, P, LL, P, P, P, P, LL, LL,
+                                          P, P, P, P, P, LL, I, I, I, I, I, P, P]
+    lib.agd_dense_pack_row_bytes.restype = LL
+    lib.agd_dense_pack_row_bytes.argtypes = [LL]
     lib.agd_csr_eval.restype = I
     lib.agd_csr_eval.argtypes = [P, P, P, P, P, P, P, LL, LL, LL, P, P, P, P, I, P, P, P, I, I, P, P]
     lib.agd_axpby.restype = I
@@ -339,6 +353,127 @@ def dense_grad_from_mult(features: torch.Tensor, mult: torch.Tensor) -> torch.Te
         3, _ptr(_red_ws(dev)), _stream(features),
     )
     _check(rc)
+    return grad
+
+
+# --- 12-bit packed bf16 shard (one-time passes + packed stream) -----------
+
+def dense_pack_hist(features: torch.Tensor) -> torch.Tensor:
+    """[128] int64 (host) counts of the high-byte magnitude (bf16 bits 14..8)."""
+    lib = load()
+    assert features.is_cuda and features.is_contiguous() and features.dtype == torch.bfloat16
+    n, d = features.shape
+    blocks = int(lib.agd_dense_pack_hist_blocks(n, d))
+    part = torch.empty((blocks, 128), dtype=torch.int64, device=features.device)
+    _check(lib.agd_dense_pack_hist(_ptr(features), n, d, _ptr(part), _stream(features)))
+    return part.sum(dim=0).cpu()
+
+
+def dense_pack_encode(features: torch.Tensor, lut_lo: int, lut_hi: int):
+    """(packed [n, row bytes] uint8, esc_count [n] int32, per-group escape
+    masks [n, row bytes / 12] uint8) for the given table."""
+    lib = load()
+    n, d = features.shape
+    row_bytes = int(lib.agd_dense_pack_row_bytes(d))
+    packed = torch.empty((n, row_bytes), dtype=torch.uint8, device=features.device)
+    esc_count = torch.empty(n, dtype=torch.int32, device=features.device)
+    flags = torch.empty((n, row_bytes // 12), dtype=torch.uint8, device=features.device)
+    _check(lib.agd_dense_pack_encode(_ptr(features), n, d, lut_lo, lut_hi,
+                                     _ptr(packed), _ptr(esc_count), _ptr(flags),
+                                     _stream(features)))
+    return packed, esc_count, flags
+
+
+def dense_pack_escapes(features: torch.Tensor, flags: torch.Tensor,
+                       rowptr: torch.Tensor, nnz: int):
+    """Row-sorted escape coordinates (col int32, val f32) for rowptr [n+1],
+    from the escape masks the encode pass wrote."""
+    lib = load()
+    n, d = features.shape
+    col = torch.empty(nnz, dtype=torch.int32, device=features.device)
+    val = torch.empty(nnz, dtype=torch.float32, device=features.device)
+    _check(lib.agd_dense_pack_escapes(_ptr(features), n, d, _ptr(flags),
+                                      _ptr(rowptr), _ptr(col), _ptr(val),
+                                      _stream(features)))
+    return col, val
+
+
+def _packed_call(pk, mode: int, *, w=None, labels=None, mask=None, sw=None,
+                 margins=None, mult=None, loss_type: int = 0,
+                 need_grad: bool = True):
+    """agd_dense_eval modes 0-3 on a PackedDense copy (same planning and
+    workspaces as the raw bf16 shard)."""
+    lib = load()
+    n, d = pk.n, pk.d
+    dev = pk.packed.device
+    acc = torch.float32
+    n_slabs = int(lib.agd_margin_slabs(n, d, 0, 1)) if mode in (0, 1) else 1
+    if mode in (0, 1):
+        margins = torch.empty(n_slabs * n, dtype=acc, device=dev)
+    loss_count = None
+    if mode != 1 and mode != 3:
+        loss_count = torch.zeros(2, dtype=torch.float64, device=dev)
+    if mode in (0, 2):
+        mult = torch.empty(n, dtype=acc, device=dev)
+    grad = part = None
+    n_rb = 1
+    if need_grad and mode != 1:
+        grad = torch.empty(d, dtype=acc, device=dev)
+        n_rb = int(lib.agd_dense_rowblocks(n, d, 0))
+        part = torch.empty(n_rb * d, dtype=acc, device=dev) if n_rb > 1 else grad
+    e = pk.esc
+    rc = lib.agd_dense_eval_packed(
+        _ptr(pk.packed), pk.lut_lo, pk.lut_hi,
+        _ptr(e["rowptr"]), _ptr(e["col"]), _ptr(e["val"]),
+        _ptr(e["colptr"]), _ptr(e["row"]), _ptr(e["cval"]), pk.nnz,
+        _ptr(labels), _ptr(mask), _ptr(sw), _ptr(w), n, d, _ptr(grad),
+        _ptr(loss_count), _ptr(margins), _ptr(mult), _ptr(part), n_rb,
+        loss_type, n_slabs, 1 if (need_grad and mode != 1) else 0,
+        int(os.environ.get("SPARKAGD_NT_LOADS", "1")),
+        mode, _ptr(_red_ws(dev)), _stream(pk.packed),
+    )
+    _check(rc)
+    return grad, loss_count, margins
+
+
+def _labels_f32(labels: torch.Tensor) -> torch.Tensor:
+    labels = labels.contiguous()
+    return labels if labels.dtype == torch.float32 else labels.to(torch.float32)
+
+
+def dense_eval_packed(pk, labels, w, loss_type, mask=None, need_grad=True,
+                      sample_weight=None):
+    if w.dtype != torch.float32:
+        raise TypeError(f"weights dtype {w.dtype} must be torch.float32 for a packed bf16 shard")
+    dev = pk.packed.device
+    grad, lc, _ = _packed_call(
+        pk, 0, w=w.contiguous(), labels=_labels_f32(labels),
+        mask=_prep_mask(mask, dev), sw=_prep_weights(sample_weight, dev),
+        loss_type=loss_type, need_grad=need_grad)
+    return grad, lc
+
+
+def dense_margins_packed(pk, v: torch.Tensor) -> torch.Tensor:
+    if v.dtype != torch.float32:
+        raise TypeError(f"vector dtype {v.dtype} must be torch.float32")
+    _, _, margins = _packed_call(pk, 1, w=v.contiguous(), need_grad=False)
+    return margins.narrow(0, 0, pk.n)
+
+
+def dense_eval_from_margins_packed(pk, margins, labels, loss_type, mask=None,
+                                   need_grad=True, sample_weight=None):
+    assert margins.dtype == torch.float32 and margins.numel() == pk.n
+    dev = pk.packed.device
+    grad, lc, _ = _packed_call(
+        pk, 2, labels=_labels_f32(labels), mask=_prep_mask(mask, dev),
+        sw=_prep_weights(sample_weight, dev), margins=margins.contiguous(),
+        loss_type=loss_type, need_grad=need_grad)
+    return grad, lc
+
+
+def dense_grad_from_mult_packed(pk, mult: torch.Tensor) -> torch.Tensor:
+    assert mult.dtype == torch.float32 and mult.numel() == pk.n
+    grad, _, _ = _packed_call(pk, 3, mult=mult.contiguous(), need_grad=True)
     return grad
 
 
@@ -1013,6 +1148,10 @@ def dense_scale_cols(features: torch.Tensor, scale: torch.Tensor,
                                   _ptr(scale), n, d, _ptr(out),
                                   _stream(features))
     _check(rc)
+    if out is features:
+        # written through its raw pointer: move the version counter so that
+        # anything cached from the old values (DenseShard's packed copy) drops
+        torch.autograd.graph.increment_version(out)
     return out
 
 

@@ -112,6 +112,7 @@ def run(
     solver: str = "direct",
     gram_op=None,
     backtrack_tol: float = 1e-10,
+    pack_dense: str | bool = "auto",
 ) -> Tuple[torch.Tensor, List[float]]:
     """Run accelerated proximal gradient descent.
 
@@ -141,7 +142,25 @@ def run(
     for non-affine updaters (L1) and when ``resume_from``/bitwise
     reproducibility against the non-tracking path is required
     (``track_margins=False``).
+
+    **Packed bf16 shards** (``pack_dense``, default auto): a GPU bf16 dense
+    shard is streamed twice per iteration and is constant for the whole
+    solve, so before the first iteration it may be re-encoded once into a
+    lossless 12-bit copy (``packing.py``) that the same kernels stream at
+    0.75x the bytes. ``"auto"`` packs when the shard is bf16 with
+    d % 8 == 0, larger than the Infinity Cache, fits a second 0.75x copy
+    with headroom, leaves its escapes under the cap, and the run plans at
+    least ``packing.PACK_BREAK_EVEN_ITERS`` iterations; ``True`` packs
+    whenever the format allows; ``False`` never packs. Nothing is packed for
+    a gradient that does not evaluate through the shard's own methods (the
+    multiclass gradient streams ``features`` itself). ``SPARKAGD_PACK_DENSE``
+    = 1 / 0 replaces the ``"auto"`` default. Direct solver only.
     """
+    if pack_dense not in ("auto", True, False):
+        raise ValueError("pack_dense must be 'auto', True or False")
+    if pack_dense == "auto" and os.environ.get("SPARKAGD_PACK_DENSE") in ("0", "1"):
+        # operator override of the default only; an explicit argument wins
+        pack_dense = os.environ["SPARKAGD_PACK_DENSE"] == "1"
     if solver not in ("direct", "gram"):
         raise ValueError("solver must be 'direct' or 'gram'")
     if solver == "gram":
@@ -179,6 +198,12 @@ def run(
         backtrack_simple = state["backtrack_simple"]
         loss_history = list(state["loss_history"])
         start_iter = state["iter"] + 1
+
+    if pack_dense is not False:
+        from .packing import apply_pack_policy
+
+        apply_pack_policy(data, pack_dense, num_iterations - start_iter + 1,
+                          gradient)
 
     eval_state = {"n": 0, "seconds": 0.0}
 
@@ -590,6 +615,7 @@ class AcceleratedGradientDescent(Optimizer):
             track_margins=c.track_margins,
             margin_refresh_every=c.margin_refresh_every,
             backtrack_tol=c.backtrack_tol,
+            pack_dense=c.pack_dense,
         )
         return weights
 

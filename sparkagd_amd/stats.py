@@ -250,6 +250,7 @@ class StandardScaler:
             out = ops.dense_scale_cols(shard.features, scale,
                                        out=shard.features if inplace else None)
             if inplace:
+                shard.unpack()  # a packed copy would hold the unscaled values
                 return shard
             return DenseShard(out, shard.labels, shard.sample_weight)
         raise TypeError(f"transform: unsupported shard type {type(shard).__name__}")
