@@ -228,16 +228,15 @@ __device__ __forceinline__ const TA* elem_at(const TA* __restrict__ A, ll r,
   else return A + r * d + c;
 }
 
-// loadW for the packed tag: one 12-B load, 10 byte-permutes + 6 bit ops, and
-// the 8 decoded values are the bf16 values bit for bit (as f32).
-template <typename TACC, bool NT>
-__device__ __forceinline__ void loadW_pk(const pk12* __restrict__ p,
-                                         TACC (&out)[8], unsigned lut_lo,
-                                         unsigned lut_hi) {
-  typedef unsigned int u32x3
-      __attribute__((ext_vector_type(3), aligned(4)));
-  const u32x3 v = NT ? __builtin_nontemporal_load((const u32x3*)p)
-                     : *(const u32x3*)p;
+typedef unsigned int pk_u32x3 __attribute__((ext_vector_type(3), aligned(4)));
+
+// Decode of one group, shared by the stream kernels and the decoder: 10
+// byte-permutes + 6 bit ops. bits[k] is element k as f32 bits (the bf16
+// pattern in the high half, zeros below).
+__device__ __forceinline__ void pk_decode_bits(const pk_u32x3 v,
+                                               unsigned (&bits)[8],
+                                               unsigned lut_lo,
+                                               unsigned lut_hi) {
   const unsigned z = v[2];
   const unsigned hA =
       __builtin_amdgcn_perm(lut_hi, lut_lo, z & 0x07070707u) |
@@ -248,11 +247,26 @@ __device__ __forceinline__ void loadW_pk(const pk12* __restrict__ p,
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const unsigned sel = ((4u + i) << 24) | ((unsigned)i << 16) | 0x0c0cu;
-    union { unsigned int u; float f; } a, b;
-    a.u = __builtin_amdgcn_perm(hA, v[0], sel);
-    b.u = __builtin_amdgcn_perm(hB, v[1], sel);
-    out[i] = (TACC)a.f;
-    out[4 + i] = (TACC)b.f;
+    bits[i] = __builtin_amdgcn_perm(hA, v[0], sel);
+    bits[4 + i] = __builtin_amdgcn_perm(hB, v[1], sel);
+  }
+}
+
+// loadW for the packed tag: one 12-B load and pk_decode_bits; the 8 decoded
+// values are the bf16 values bit for bit (as f32).
+template <typename TACC, bool NT>
+__device__ __forceinline__ void loadW_pk(const pk12* __restrict__ p,
+                                         TACC (&out)[8], unsigned lut_lo,
+                                         unsigned lut_hi) {
+  const pk_u32x3 v = NT ? __builtin_nontemporal_load((const pk_u32x3*)p)
+                        : *(const pk_u32x3*)p;
+  unsigned bits[8];
+  pk_decode_bits(v, bits, lut_lo, lut_hi);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    union { unsigned int u; float f; } a;
+    a.u = bits[k];
+    out[k] = (TACC)a.f;
   }
 }
 
@@ -1858,6 +1872,59 @@ __global__ __launch_bounds__(BLOCK) void k_pack_fix_grad(
   }
 }
 
+// Decode: packed groups back to bf16, bit for bit (escapes come out as +0.0
+// and k_pack_fix_decode puts them back). One thread per real 8-element
+// group, grid-stride over n * d/8 groups; the row padding is never read.
+// (r, c) = (row, group in row) advances by the stride's own quotient and
+// remainder, so the loop has no division. One 12-B load, pk_decode_bits,
+// four permutes that keep the high halves, one 16-B store: out + 8 g is
+// 16-B aligned because d % 8 == 0 and the base is.
+__global__ __launch_bounds__(BLOCK) void k_dense_pack_decode(
+    const pk12* __restrict__ P, ll n_groups, ll gpr, unsigned lut_lo,
+    unsigned lut_hi, ubf16* __restrict__ out) {
+  using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+  const ll gs = pk_row_groups(gpr << 3);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll dr = stride / gpr, dc = stride - dr * gpr;
+  ll g = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  ll r = g / gpr, c = g - r * gpr;
+  for (; g < n_groups; g += stride) {
+    const pk_u32x3 v = *(const pk_u32x3*)(P + r * gs + c);
+    unsigned bits[8];
+    pk_decode_bits(v, bits, lut_lo, lut_hi);
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)  // bytes 2,3 of element 2i, then of 2i+1
+      o[i] = __builtin_amdgcn_perm(bits[2 * i + 1], bits[2 * i], 0x07060302u);
+    *(u32x4*)(out + g * 8) = o;
+    r += dr;
+    c += dc;
+    if (c >= gpr) {
+      c -= gpr;
+      ++r;
+    }
+  }
+}
+
+// out[r * d + col[k]] = high half of val[k] over the row's escapes (one wave
+// per row with escapes, the k_pack_fix_margins skeleton). val holds bf16
+// values widened to f32, so the shift is exact: bit moves only.
+__global__ __launch_bounds__(BLOCK) void k_pack_fix_decode(
+    const int* __restrict__ rowptr, const int* __restrict__ col,
+    const float* __restrict__ val, ll n, ll d, ubf16* __restrict__ out) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / WAVE;
+  const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
+  for (ll r = wave_gid; r < n; r += n_waves) {
+    const int k_lo = rowptr[r], k_hi = rowptr[r + 1];
+    for (int k = k_lo + lane; k < k_hi; k += WAVE) {
+      const ll c = col[k];
+      if (c >= 0 && c < d)  // keeps the store inside the row
+        out[r * d + c] = (ubf16)(__float_as_uint(val[k]) >> 16);
+    }
+  }
+}
+
 // Escape side lists + decode table of a packed shard (dense_eval_t).
 struct PackSide {
   unsigned lut_lo, lut_hi;
@@ -2165,6 +2232,36 @@ extern "C" int agd_dense_pack_escapes(const void* A, long long n, long long d,
                      (const unsigned char*)flags, (const int*)rowptr, (int*)col,
                      (float*)val);
   HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// packed [n, agd_dense_pack_row_bytes(d)] bytes -> out [n, d] bf16, bit for
+// bit: the group decode, then the row-sorted escapes (CSR side list; ignored
+// when nnz == 0) stored over the +0.0 they decoded to, in stream order.
+extern "C" int agd_dense_pack_decode(const void* packed, unsigned lut_lo,
+                                     unsigned lut_hi, const void* esc_rowptr,
+                                     const void* esc_col, const void* esc_val,
+                                     long long esc_nnz, long long n,
+                                     long long d, void* out, void* stream) {
+  if (!pack_shape_ok("agd_dense_pack_decode", packed, n, d)) return 2;
+  if (!pack_shape_ok("agd_dense_pack_decode(out)", out, n, d)) return 2;
+  if (!pack_lut_ok("agd_dense_pack_decode", lut_lo)) return 2;
+  if (esc_nnz > 0 && (!esc_rowptr || !esc_col || !esc_val)) {
+    snprintf(g_err, sizeof(g_err), "agd_dense_pack_decode: escape lists missing (nnz=%lld)", esc_nnz);
+    return 2;
+  }
+  const ll n_groups = n * (d / 8);
+  hipLaunchKernelGGL(k_dense_pack_decode, dim3(grid_for(n_groups, (ll)BLOCK * 4)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, (const pk12*)packed,
+                     n_groups, (ll)(d / 8), lut_lo, lut_hi, (ubf16*)out);
+  HIP_CHECK(hipGetLastError());
+  if (esc_nnz > 0) {
+    hipLaunchKernelGGL(k_pack_fix_decode, dim3(grid_for(n, WAVES_PER_BLOCK)),
+                       dim3(BLOCK), 0, (hipStream_t)stream,
+                       (const int*)esc_rowptr, (const int*)esc_col,
+                       (const float*)esc_val, (ll)n, (ll)d, (ubf16*)out);
+    HIP_CHECK(hipGetLastError());
+  }
   return 0;
 }
 

@@ -59,7 +59,9 @@ def _shard_feature_dtype(shard) -> torch.dtype:
     if getattr(shard, "kind", None) == "mixed":
         dts = [_shard_feature_dtype(p) for p in shard.parts]
         return torch.float64 if torch.float64 in dts else dts[0]
-    for attr in ("features", "features_host", "val"):
+    if getattr(shard, "kind", None) == "dense_streamed":
+        return shard.feature_dtype  # features_host may be released
+    for attr in ("features", "val"):
         t = getattr(shard, attr, None)
         if t is not None:
             return t.dtype

@@ -112,7 +112,7 @@ def csr_eval(
 
 
 # Packed bf16 shards (packing.PackedDense): GPU only; DenseShard routes here
-# when it holds a valid packed copy.
+# when it holds a valid packed copy, HostStreamedDenseShard per packed chunk.
 def dense_eval_packed(pk, labels, w, loss_type, mask=None, need_grad=True,
                       sample_weight=None):
     return _get_hip().dense_eval_packed(pk, labels, w, loss_type, mask,
@@ -131,6 +131,17 @@ def dense_eval_from_margins_packed(pk, margins, labels, loss_type, mask=None,
 
 def dense_grad_from_mult_packed(pk, mult: torch.Tensor) -> torch.Tensor:
     return _get_hip().dense_grad_from_mult_packed(pk, mult)
+
+
+def dense_pack_decode(pk, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """bf16 [n, d] from a packed copy, bit for bit: the HIP decoder on the
+    GPU, ``packing.decode_torch`` elsewhere."""
+    if _use_hip(pk.packed):
+        return _get_hip().dense_pack_decode(pk, out)
+    from ..packing import decode_torch
+
+    dec = decode_torch(pk.packed, pk.table, pk.d, pk.esc)
+    return dec if out is None else out.copy_(dec)
 
 
 def dense_margins(features: torch.Tensor, v: torch.Tensor) -> torch.Tensor:

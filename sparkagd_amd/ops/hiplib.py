@@ -70,6 +70,8 @@ def load() -> ctypes.CDLL:
                                           P, P, P, P, P, LL, I, I, I, I, I, P, P]
     lib.agd_dense_pack_row_bytes.restype = LL
     lib.agd_dense_pack_row_bytes.argtypes = [LL]
+    lib.agd_dense_pack_decode.restype = I
+    lib.agd_dense_pack_decode.argtypes = [P, U, U, P, P, P, LL, LL, LL, P, P]
     lib.agd_csr_eval.restype = I
     lib.agd_csr_eval.argtypes = [P, P, P, P, P, P, P, LL, LL, LL, P, P, P, P, I, P, P, P, I, I, P, P]
     lib.agd_axpby.restype = I
@@ -396,6 +398,25 @@ def dense_pack_escapes(features: torch.Tensor, flags: torch.Tensor,
                                       _ptr(rowptr), _ptr(col), _ptr(val),
                                       _stream(features)))
     return col, val
+
+
+def dense_pack_decode(pk, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The bf16 [n, d] matrix a PackedDense copy was built from, bit for bit
+    (escapes included); ``out`` decodes into an existing buffer."""
+    lib = load()
+    dev = pk.packed.device
+    assert pk.packed.is_cuda and pk.packed.is_contiguous()
+    assert tuple(pk.packed.shape) == (pk.n, int(lib.agd_dense_pack_row_bytes(pk.d)))
+    if out is None:
+        out = torch.empty((pk.n, pk.d), dtype=torch.bfloat16, device=dev)
+    assert (out.dtype == torch.bfloat16 and out.device == dev
+            and tuple(out.shape) == (pk.n, pk.d) and out.is_contiguous())
+    e = pk.esc
+    _check(lib.agd_dense_pack_decode(
+        _ptr(pk.packed), pk.lut_lo, pk.lut_hi, _ptr(e["rowptr"]),
+        _ptr(e["col"]), _ptr(e["val"]), pk.nnz, pk.n, pk.d, _ptr(out),
+        _stream(pk.packed)))
+    return out
 
 
 def _packed_call(pk, mode: int, *, w=None, labels=None, mask=None, sw=None,

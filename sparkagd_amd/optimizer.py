@@ -153,7 +153,9 @@ def run(
     least ``packing.PACK_BREAK_EVEN_ITERS`` iterations; ``True`` packs
     whenever the format allows; ``False`` never packs. Nothing is packed for
     a gradient that does not evaluate through the shard's own methods (the
-    multiclass gradient streams ``features`` itself). ``SPARKAGD_PACK_DENSE``
+    multiclass gradient streams ``features`` itself). A host-streamed bf16
+    shard on a GPU is packed under ``True`` only (its bytes then cross the
+    host link at 0.75x); ``"auto"`` leaves it raw. ``SPARKAGD_PACK_DENSE``
     = 1 / 0 replaces the ``"auto"`` default. Direct solver only.
     """
     if pack_dense not in ("auto", True, False):

@@ -151,21 +151,16 @@ def pack_refusal(features: torch.Tensor) -> Optional[str]:
     return None
 
 
-def pack_features(features: torch.Tensor) -> Tuple[Optional[PackedDense], Optional[str]]:
-    """Build the packed copy; returns ``(None, reason)`` when refused."""
-    import time
-
-    why = pack_refusal(features)
-    if why is not None:
-        return None, why
+def encode_with_table(features: torch.Tensor, table: Sequence[int],
+                      n_esc: int) -> Tuple[torch.Tensor, dict]:
+    """The table-given half of a pack: the packed bytes of ``features`` (a
+    whole shard, or one chunk of a streamed one) under ``table`` and the
+    escape side lists, rows local to ``features``. ``n_esc`` is the number of
+    elements whose high byte is not in the table (known from the histogram).
+    Work is queued on the current stream; the caller synchronises."""
     from . import ops
 
-    t0 = time.perf_counter()
     n, d = features.shape
-    table, n_esc = choose_pack_table(_hist(features).tolist())
-    if n_esc > PACK_ESCAPE_CAP * n * d:
-        return None, (f"escape fraction {n_esc / (n * d):.3e} exceeds "
-                      f"{PACK_ESCAPE_CAP:.3e}")
     esc = _no_escapes()
     if ops._use_hip(features):
         hip = ops._get_hip()
@@ -186,23 +181,73 @@ def pack_features(features: torch.Tensor) -> Tuple[Optional[PackedDense], Option
             esc = {"rowptr": rowptr, "col": col, "val": val, "colptr": colptr,
                    "row": rows[order].contiguous(), "cval": val[order].contiguous()}
         del flags
-        if features.is_cuda:
-            torch.cuda.synchronize(features.device)
     else:
         packed, esc_mask = _encode_torch(features, table)
         if n_esc > 0:
             rows, cols = esc_mask.nonzero(as_tuple=True)
             val = features[rows, cols].to(torch.float32)
-            rowptr = torch.zeros(n + 1, dtype=torch.int32)
+            rowptr = torch.zeros(n + 1, dtype=torch.int32, device=rows.device)
             rowptr[1:] = torch.cumsum(torch.bincount(rows, minlength=n), 0)
             order = torch.sort(cols, stable=True).indices
-            colptr = torch.zeros(d + 1, dtype=torch.int32)
+            colptr = torch.zeros(d + 1, dtype=torch.int32, device=rows.device)
             colptr[1:] = torch.cumsum(torch.bincount(cols, minlength=d), 0)
             esc = {"rowptr": rowptr, "col": cols.to(torch.int32), "val": val,
                    "colptr": colptr, "row": rows[order].to(torch.int32),
                    "cval": val[order]}
+    return packed, esc
+
+
+def escape_cap_refusal(n_esc: int, n: int, d: int) -> Optional[str]:
+    """The refusal reason when ``n_esc`` escapes exceed the cap, or None."""
+    if n_esc > PACK_ESCAPE_CAP * n * d:
+        return (f"escape fraction {n_esc / (n * d):.3e} exceeds "
+                f"{PACK_ESCAPE_CAP:.3e}")
+    return None
+
+
+def pack_features(features: torch.Tensor) -> Tuple[Optional[PackedDense], Optional[str]]:
+    """Build the packed copy; returns ``(None, reason)`` when refused."""
+    import time
+
+    why = pack_refusal(features)
+    if why is not None:
+        return None, why
+    t0 = time.perf_counter()
+    n, d = features.shape
+    table, n_esc = choose_pack_table(_hist(features).tolist())
+    why = escape_cap_refusal(n_esc, n, d)
+    if why is not None:
+        return None, why
+    packed, esc = encode_with_table(features, table, n_esc)
+    if features.is_cuda:
+        torch.cuda.synchronize(features.device)
     return PackedDense(packed, table, n, d, esc, n_esc,
                        time.perf_counter() - t0), None
+
+
+def decode_torch(packed: torch.Tensor, table: Sequence[int], d: int,
+                 esc: Optional[dict] = None) -> torch.Tensor:
+    """Plain-torch decoder: packed ``[n, pack_row_bytes(d)]`` uint8 back to
+    the bf16 ``[n, d]`` matrix, bit for bit, with the escapes of the CSR side
+    list ``esc`` (``rowptr/col/val``) scattered back in. Integer moves only,
+    so NaN payloads, infinities and -0.0 survive."""
+    n = packed.shape[0]
+    p = packed.view(n, -1, 12)[:, :d // 8].to(torch.int32)
+    tab = torch.as_tensor(list(table), dtype=torch.int32, device=packed.device)
+    bits = torch.empty((n, d // 8, 8), dtype=torch.int32, device=packed.device)
+    for k in range(8):
+        code = (p[:, :, 8 + (k & 3)] >> (4 * (k >> 2))) & 0xF
+        high = tab[(code & 7).long()] | ((code >> 3) << 7)
+        bits[:, :, k] = (high << 8) | p[:, :, k]
+    bits = bits.view(n, d)
+    if esc is not None and esc.get("col") is not None and esc["col"].numel():
+        counts = torch.diff(esc["rowptr"].long())
+        rows = torch.repeat_interleave(
+            torch.arange(n, device=packed.device), counts)
+        bits[rows, esc["col"].long()] = \
+            (esc["val"].view(torch.int32) >> 16) & 0xFFFF
+    # two's-complement wrap of the 16-bit pattern into int16, then reinterpret
+    return bits.to(torch.int16).view(torch.bfloat16)
 
 
 def auto_pack_wanted(features: torch.Tensor, planned_iterations: int) -> bool:
@@ -259,10 +304,18 @@ def apply_pack_policy(data, pack_dense, planned_iterations: int,
     the dense parts of a MixedShard). Nothing is packed, under ``"auto"`` or
     ``True``, for a ``gradient`` that does not stream through the shard's
     routed methods. A refused pack leaves the shard on the raw path and its
-    reason in ``pack_refused``."""
+    reason in ``pack_refused``.
+
+    A host-streamed shard on a GPU is packed under ``True`` only (its bytes
+    then cross the host link at 0.75x); ``"auto"`` leaves it raw, because
+    its break-even against the one-time pack is not part of the gate yet."""
     if pack_dense is False:
         return
     if gradient is not None and not gradient_streams_shard(gradient):
+        return
+    if getattr(data, "kind", None) == "dense_streamed":
+        if pack_dense is True and data.streams_packed_on_gpu and not data.is_packed:
+            data.pack()
         return
     for shard in _dense_parts(data):
         if shard.is_packed:

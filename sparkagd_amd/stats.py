@@ -98,7 +98,8 @@ def _local_moments(shard):
 
         shard._for_each_chunk(step)
         if acc is None:
-            acc = _dense_moments(shard.features_host[:0].to(shard.device))
+            acc = _dense_moments(torch.empty(
+                (0, shard.d), dtype=shard.feature_dtype, device=shard.device))
         return acc
     if isinstance(shard, CSRShard):
         return _csr_moments(shard)
@@ -162,12 +163,12 @@ def _scale_dtype(shard) -> torch.dtype:
         dts = {_scale_dtype(p) for p in shard.parts}
         return torch.float64 if dts == {torch.float64} else torch.float32
     if isinstance(shard, HostStreamedDenseShard):
-        t = shard.features_host
+        dtype = shard.feature_dtype  # features_host may be released
     elif isinstance(shard, CSRShard):
-        t = shard.val
+        dtype = shard.val.dtype
     else:
-        t = shard.features
-    return torch.float64 if t.dtype == torch.float64 else torch.float32
+        dtype = shard.features.dtype
+    return torch.float64 if dtype == torch.float64 else torch.float32
 
 
 class StandardScaler:
