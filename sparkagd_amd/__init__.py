@@ -50,6 +50,8 @@ from .evaluation import (BinaryMetrics, MulticlassMetrics, RegressionMetrics,
                          evaluate)
 from .streaming import HostStreamedDenseShard
 from .stats import ColumnSummary, StandardScaler, column_stats
+from .models.multitask import MultiTaskGradient, PerTaskUpdater
+from .model_selection import CVResult, assign_folds, cross_validate
 
 __version__ = "0.2.0"
 
@@ -101,4 +103,9 @@ __all__ = [
     "BinaryMetrics",
     "RegressionMetrics",
     "MulticlassMetrics",
+    "MultiTaskGradient",
+    "PerTaskUpdater",
+    "cross_validate",
+    "assign_folds",
+    "CVResult",
 ]

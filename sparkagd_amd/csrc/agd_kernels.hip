@@ -3961,3 +3961,361 @@ extern "C" int agd_csr_grad_from_mult(
   HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Multi-task family: R independent binary problems (a (lambda, fold) sweep)
+// sharing one shard. Margins/gradient reuse the multinomial [n, KC] plumbing
+// (hipBLASLt GEMMs, k_dense_margins_multi / k_grad_multi, the CSR gathers);
+// these are the two pieces that differ: the n-space multiplier with a
+// per-column training set and the prox with a per-column lambda.
+// ---------------------------------------------------------------------------
+
+// Grid cap of the task multiplier: each block leaves KC + 1 f64 partials, so
+// the workspace is TASKS_MAX_GRID * (KC + 1) doubles (sized by the wrapper
+// through agd_tasks_ws_doubles) and the one-block finish reads all of it.
+#define TASKS_MAX_GRID 1024
+
+static inline int tasks_grid(ll work_items, ll per_block) {
+  ll g = (work_items + per_block - 1) / per_block;
+  if (g > TASKS_MAX_GRID) g = TASKS_MAX_GRID;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+extern "C" long long agd_tasks_ws_doubles(int kc) {
+  return (long long)TASKS_MAX_GRID * ((long long)kc + 1);
+}
+
+// One 4-column group of one row: a_ir from the fold test, the binary
+// loss_mult per live column, M scaled by s_i * scale_r, the unscaled
+// weighted loss into the caller's f64 partials.
+__device__ __forceinline__ void tasks_group(
+    const float* __restrict__ zp, float y, float s, int f, int loss_type,
+    int invert, const int (&h)[4], const float (&sc)[4], const bool (&live)[4],
+    float* __restrict__ mp, double (&ls)[4]) {
+  using f32x4 = __attribute__((ext_vector_type(4))) float;
+  const f32x4 zv = *(const f32x4*)zp;
+  f32x4 mv = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const bool train = (f != h[j]);
+    if (live[j] && (train != (invert != 0))) {
+      float m, l;
+      loss_mult<float>(loss_type, zv[j], y, m, l);
+      mv[j] = m * s * sc[j];
+      ls[j] += (double)l * (double)s;
+    }
+  }
+  if (mp) *(f32x4*)mp = mv;
+}
+
+// KC in {4, 8, 16, 32}: elementwise over the n*KC/4 column groups with 16-B
+// accesses. The grid stride (gridDim*BLOCK groups) is a multiple of KC/4, so
+// a thread keeps ONE column group for its whole loop: 4 f64 loss partials in
+// registers instead of KC, and holdout/scale are read once. Lanes with equal
+// (lane % (KC/4)) own the same columns; the xor-shuffle tree stops at KC/4.
+template <int KC>
+__global__ __launch_bounds__(BLOCK) void k_multiplier_tasks(
+    const float* __restrict__ Z, const float* __restrict__ labels,
+    const unsigned char* __restrict__ mask,
+    const float* __restrict__ sample_weight, const int* __restrict__ fold_id,
+    const int* __restrict__ holdout, const float* __restrict__ task_scale,
+    int loss_type, int invert, ll n, int R, float* __restrict__ M,
+    double* __restrict__ part, double* __restrict__ cnt_part) {
+  constexpr int G4 = KC / 4;
+  static_assert(BLOCK % G4 == 0 && WAVE % G4 == 0, "column group must tile");
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const int c0 = (int)(threadIdx.x % G4) * 4;
+  int h[4];
+  float sc[4];
+  bool live[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int r = c0 + j;
+    live[j] = r < R;
+    h[j] = (live[j] && holdout) ? holdout[r] : -1;
+    sc[j] = live[j] ? task_scale[r] : 0.f;
+  }
+  double ls[4] = {0.0, 0.0, 0.0, 0.0};
+  double cnt = 0.0;
+  const ll ngroups = n * G4;
+  const ll stride = (ll)gridDim.x * BLOCK;
+  for (ll g = gid; g < ngroups; g += stride) {
+    const ll i = g / G4;
+    float* mp = M ? M + g * 4 : nullptr;
+    if (mask && !mask[i]) {
+      using f32x4 = __attribute__((ext_vector_type(4))) float;
+      if (mp) *(f32x4*)mp = f32x4{0.f, 0.f, 0.f, 0.f};
+      continue;
+    }
+    const float s = sample_weight ? sample_weight[i] : 1.0f;
+    // no fold vector: no row is in any fold (never equals a holdout, -1 too)
+    const int f = fold_id ? fold_id[i] : -2;
+    if (c0 == 0) cnt += (double)s;
+    tasks_group(Z + g * 4, labels[i], s, f, loss_type, invert, h, sc, live,
+                mp, ls);
+  }
+  __shared__ double lds[WAVES_PER_BLOCK][KC];
+  __shared__ double ldc[WAVES_PER_BLOCK];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    double v = ls[j];
+#pragma unroll
+    for (int off = 32; off >= G4; off >>= 1) v += __shfl_xor(v, off, WAVE);
+    if (lane < G4) lds[wid][lane * 4 + j] = v;
+  }
+  cnt = wave_reduce_sum(cnt);
+  if (lane == 0) ldc[wid] = cnt;
+  __syncthreads();
+  if (threadIdx.x < KC) {
+    double v = lds[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < WAVES_PER_BLOCK; ++w) v += lds[w][threadIdx.x];
+    part[(ll)blockIdx.x * KC + threadIdx.x] = v;
+  }
+  if (threadIdx.x == 0) {
+    double v = ldc[0];
+#pragma unroll
+    for (int w = 1; w < WAVES_PER_BLOCK; ++w) v += ldc[w];
+    cnt_part[blockIdx.x] = v;
+  }
+}
+
+// Any 4-aligned KC (> 32 in practice): one wave per row, lane l owns the
+// column group at chunk + 4l; the column axis is walked in chunks of 256 so
+// the per-lane partials stay 4 f64 for any KC. Waves of a block hold the
+// same columns lane for lane, so the block stage is a 4-term LDS sum.
+#define TASKS_CHUNK (WAVE * 4)
+__global__ __launch_bounds__(BLOCK) void k_multiplier_tasks_anyk(
+    const float* __restrict__ Z, const float* __restrict__ labels,
+    const unsigned char* __restrict__ mask,
+    const float* __restrict__ sample_weight, const int* __restrict__ fold_id,
+    const int* __restrict__ holdout, const float* __restrict__ task_scale,
+    int loss_type, int invert, ll n, int R, int KC, float* __restrict__ M,
+    double* __restrict__ part, double* __restrict__ cnt_part) {
+  using f32x4 = __attribute__((ext_vector_type(4))) float;
+  __shared__ double lds[WAVES_PER_BLOCK][TASKS_CHUNK];
+  __shared__ double ldc[WAVES_PER_BLOCK];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + wid;
+  const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
+  double cnt = 0.0;
+  for (int chunk = 0; chunk < KC; chunk += TASKS_CHUNK) {
+    const int c0 = chunk + lane * 4;
+    const bool active = c0 < KC;  // KC % 4 == 0: the whole group is inside
+    int h[4];
+    float sc[4];
+    bool live[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int r = c0 + j;
+      live[j] = active && r < R;
+      h[j] = (live[j] && holdout) ? holdout[r] : -1;
+      sc[j] = live[j] ? task_scale[r] : 0.f;
+    }
+    double ls[4] = {0.0, 0.0, 0.0, 0.0};
+    for (ll i = wave_gid; i < n; i += n_waves) {
+      float* mp = (M && active) ? M + i * KC + c0 : nullptr;
+      if (mask && !mask[i]) {
+        if (mp) *(f32x4*)mp = f32x4{0.f, 0.f, 0.f, 0.f};
+        continue;
+      }
+      const float s = sample_weight ? sample_weight[i] : 1.0f;
+      const int f = fold_id ? fold_id[i] : -2;
+      if (chunk == 0 && lane == 0) cnt += (double)s;
+      if (active)
+        tasks_group(Z + i * KC + c0, labels[i], s, f, loss_type, invert, h,
+                    sc, live, mp, ls);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) lds[wid][lane * 4 + j] = ls[j];
+    __syncthreads();
+    const int c = chunk + threadIdx.x;  // BLOCK == TASKS_CHUNK columns
+    if (c < KC) {
+      double v = lds[0][threadIdx.x];
+#pragma unroll
+      for (int w = 1; w < WAVES_PER_BLOCK; ++w) v += lds[w][threadIdx.x];
+      part[(ll)blockIdx.x * KC + c] = v;
+    }
+    __syncthreads();
+  }
+  static_assert(BLOCK == TASKS_CHUNK, "one finishing thread per chunk column");
+  cnt = wave_reduce_sum(cnt);
+  if (lane == 0) ldc[wid] = cnt;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double v = ldc[0];
+#pragma unroll
+    for (int w = 1; w < WAVES_PER_BLOCK; ++w) v += ldc[w];
+    cnt_part[blockIdx.x] = v;
+  }
+}
+
+// One-block finish of the task multiplier (OVERWRITES its outputs):
+//   task_loss[r]  = sum_b part[b, r]           (fixed order: bitwise stable)
+//   loss_count[0] = sum_r task_scale[r] * task_loss[r]
+//   loss_count[1] = sum_b cnt_part[b]
+// Wave w of the block sums blocks w, w+4, ... of 64 columns at a time.
+__global__ __launch_bounds__(BLOCK) void k_reduce_task_partials(
+    const double* __restrict__ part, const double* __restrict__ cnt_part,
+    int nblocks, int KC, int R, const float* __restrict__ task_scale,
+    double* __restrict__ task_loss, double* __restrict__ loss_count) {
+  __shared__ double lds[WAVES_PER_BLOCK][WAVE];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  double tot = 0.0;
+  for (int chunk = 0; chunk < KC; chunk += WAVE) {
+    const int c = chunk + lane;
+    double a = 0.0;
+    if (c < KC)
+      for (int b = wid; b < nblocks; b += WAVES_PER_BLOCK)
+        a += part[(ll)b * KC + c];
+    lds[wid][lane] = a;
+    __syncthreads();
+    if (wid == 0 && c < R) {
+      double v = lds[0][lane];
+#pragma unroll
+      for (int w = 1; w < WAVES_PER_BLOCK; ++w) v += lds[w][lane];
+      task_loss[c] = v;
+      tot += (double)task_scale[c] * v;
+    }
+    __syncthreads();
+  }
+  if (wid == 0) {
+    tot = wave_reduce_sum(tot);
+    if (lane == 0) loss_count[0] = tot;
+  }
+  double acc[1] = {0.0};
+  for (int b = threadIdx.x; b < nblocks; b += BLOCK) acc[0] += cnt_part[b];
+  block_reduce_partial<1>(acc, loss_count + 1);  // blockIdx.x == 0
+}
+
+// M may be null (loss-only call). task_loss f64[R] and loss_count f64[2] are
+// overwritten. ws holds agd_tasks_ws_doubles(kc) doubles.
+extern "C" int agd_multiplier_tasks(
+    const void* Z, const void* labels, const void* mask,
+    const void* sample_weight, const void* fold_id, const void* holdout,
+    const void* task_scale, int loss_type, int invert, long long n, int R,
+    int kc, void* M, void* task_loss, void* loss_count, void* ws,
+    void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (kc < 4 || (kc & 3) || R < 1 || R > kc || n < 0) {
+    snprintf(g_err, sizeof(g_err), "multiplier_tasks: bad R %d / KC %d / n %lld",
+             R, kc, n);
+    return 2;
+  }
+  if (loss_type < 0 || loss_type > LOSS_SMOOTH_HINGE) {
+    snprintf(g_err, sizeof(g_err), "multiplier_tasks: bad loss_type %d", loss_type);
+    return 2;
+  }
+  double* part = (double*)ws;
+  double* cnt_part = part + (ll)TASKS_MAX_GRID * kc;
+  int grid;
+#define LAUNCH_MT(KCV)                                                        \
+  grid = tasks_grid(n * (KCV / 4), BLOCK);                                    \
+  hipLaunchKernelGGL((k_multiplier_tasks<KCV>), dim3(grid), dim3(BLOCK), 0,   \
+                     s, (const float*)Z, (const float*)labels,                \
+                     (const unsigned char*)mask, (const float*)sample_weight, \
+                     (const int*)fold_id, (const int*)holdout,                \
+                     (const float*)task_scale, loss_type, invert, (ll)n, R,   \
+                     (float*)M, part, cnt_part)
+  switch (kc) {
+    case 4: LAUNCH_MT(4); break;
+    case 8: LAUNCH_MT(8); break;
+    case 16: LAUNCH_MT(16); break;
+    case 32: LAUNCH_MT(32); break;
+    default:
+      grid = tasks_grid(n, WAVES_PER_BLOCK);
+      hipLaunchKernelGGL(k_multiplier_tasks_anyk, dim3(grid), dim3(BLOCK), 0,
+                         s, (const float*)Z, (const float*)labels,
+                         (const unsigned char*)mask,
+                         (const float*)sample_weight, (const int*)fold_id,
+                         (const int*)holdout, (const float*)task_scale,
+                         loss_type, invert, (ll)n, R, kc, (float*)M, part,
+                         cnt_part);
+      break;
+  }
+#undef LAUNCH_MT
+  hipLaunchKernelGGL(k_reduce_task_partials, dim3(1), dim3(BLOCK), 0, s, part,
+                     cnt_part, grid, kc, R, (const float*)task_scale,
+                     (double*)task_loss, (double*)loss_count);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// k_prox with a per-task lambda: w is the flat feature-major [d, R] block, so
+// element j belongs to task j % R. The task index of a thread's vector is
+// carried along the grid-stride loop (one 64-bit modulo per thread, not one
+// per element); lam/lam2 are R-entry f64 device vectors (cache-resident).
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_prox_tasks(
+    int kind, const T* __restrict__ w, const T* __restrict__ g, double step,
+    const double* __restrict__ lam, const double* __restrict__ lam2, int R,
+    T* __restrict__ out, double* __restrict__ reg_part, ll n) {
+  constexpr int VE = 16 / sizeof(T);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const T ts = (T)step;
+  double racc = 0.0;
+  const ll nv = n / VE;
+  int r0 = (int)((gid * VE) % R);
+  const int dr = (int)((stride * VE) % R);
+  for (ll i = gid; i < nv; i += stride) {
+    T wv[VE], gv[VE], ov[VE];
+    loadAcc<T, VE>(w + i * VE, wv);
+    loadAcc<T, VE>(g + i * VE, gv);
+    int r = r0;
+#pragma unroll
+    for (int k = 0; k < VE; ++k) {
+      ov[k] = prox_elem(kind, wv[k], gv[k], ts, (T)lam[r], (T)lam2[r], racc);
+      if (++r == R) r = 0;
+    }
+    storeAcc<T, VE>(out + i * VE, ov);
+    r0 += dr;
+    if (r0 >= R) r0 -= R;
+  }
+  const ll t = nv * VE + gid;
+  if (t < n) {
+    const int r = (int)(t % R);
+    out[t] = prox_elem(kind, w[t], g[t], ts, (T)lam[r], (T)lam2[r], racc);
+  }
+  if (kind != PROX_SIMPLE) {
+    double acc[1] = {racc};
+    block_reduce_partial<1>(acc, reg_part);
+  }
+}
+
+// reg (double[1]) must be zeroed by the caller; lam / lam2 are f64[R] device.
+extern "C" int agd_prox_tasks(int kind, const void* w, const void* g,
+                              double step, const void* lam, const void* lam2,
+                              int R, void* out, void* reg, long long n,
+                              int dtype, void* red_ws, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (R < 1 || lam == nullptr || lam2 == nullptr) {
+    snprintf(g_err, sizeof(g_err), "agd_prox_tasks: bad R %d or null lambdas", R);
+    return 2;
+  }
+  const int grid = grid_for(n, BLOCK * 4);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_prox_tasks<float>), dim3(grid), dim3(BLOCK), 0, s,
+                       kind, (const float*)w, (const float*)g, step,
+                       (const double*)lam, (const double*)lam2, R, (float*)out,
+                       (double*)red_ws, (ll)n);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_prox_tasks<double>), dim3(grid), dim3(BLOCK), 0, s,
+                       kind, (const double*)w, (const double*)g, step,
+                       (const double*)lam, (const double*)lam2, R,
+                       (double*)out, (double*)red_ws, (ll)n);
+  else {
+    snprintf(g_err, sizeof(g_err), "agd_prox_tasks: bad dtype %d", dtype);
+    return 2;
+  }
+  if (kind != PROX_SIMPLE)
+    hipLaunchKernelGGL((k_reduce_partials<1>), dim3(1), dim3(BLOCK), 0, s,
+                       (double*)red_ws, grid, (double*)reg);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}

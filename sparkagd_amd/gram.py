@@ -220,6 +220,11 @@ def run_gram(
     surface as optimizer.run; same AT/backtracking/restart state machine;
     returns (weights, loss_history))."""
     comm = comm or Communicator()
+    if getattr(gradient, "IS_MULTITASK", False):
+        raise ValueError(
+            "MultiTaskGradient runs on the direct solver only "
+            "(solver='direct'); the Gram solver does not carry per-task "
+            "training sets")
     if not getattr(updater, "AFFINE_PROX", False):
         raise ValueError("run_gram requires an affine prox updater (Simple/SquaredL2)")
     if getattr(data, "kind", None) == "intercept":

@@ -139,6 +139,14 @@ def load() -> ctypes.CDLL:
     lib.agd_csr_grad_from_mult.restype = I
     lib.agd_csr_grad_from_mult.argtypes = [P, P, P, P, LL, LL, P, P, P, P, I,
                                            P, P, P, LL, LL, I, P, P, P]
+    # multi-task family (ops/multitask.py)
+    lib.agd_tasks_ws_doubles.restype = LL
+    lib.agd_tasks_ws_doubles.argtypes = [I]
+    lib.agd_multiplier_tasks.restype = I
+    lib.agd_multiplier_tasks.argtypes = [P, P, P, P, P, P, P, I, I, LL, I, I,
+                                         P, P, P, P, P]
+    lib.agd_prox_tasks.restype = I
+    lib.agd_prox_tasks.argtypes = [I, P, P, D, P, P, I, P, P, LL, I, P, P]
 
     _lib = lib
     return lib
@@ -627,6 +635,92 @@ def multiplier_multi(
                                   _ptr(_red_ws(dev)), _stream(margins_padded_flat))
     _check(rc)
     return M, loss_count
+
+
+_tasks_ws_cache = {}
+
+
+def _tasks_ws(device, kc: int) -> torch.Tensor:
+    """Per-(device, KC) f64 partials of the task multiplier: KC + 1 per
+    block, too many for ``_red_ws``; the library names the size."""
+    t = _tasks_ws_cache.get((device, kc))
+    if t is None:
+        t = torch.empty(int(load().agd_tasks_ws_doubles(kc)),
+                        dtype=torch.float64, device=device)
+        _tasks_ws_cache[(device, kc)] = t
+    return t
+
+
+def multiplier_tasks(
+    margins_padded_flat: torch.Tensor,
+    labels: torch.Tensor,
+    loss_type: int,
+    r: int,
+    kc: int,
+    task_scale: torch.Tensor,
+    mask: Optional[torch.Tensor] = None,
+    sample_weight: Optional[torch.Tensor] = None,
+    fold_id: Optional[torch.Tensor] = None,
+    holdout: Optional[torch.Tensor] = None,
+    invert: bool = False,
+    need_mult: bool = True,
+) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
+    """(M [n*kc] f32 or None, task_loss f64[r], loss_count f64[2]) from padded
+    margins of ``r`` binary tasks — the n-space stage of MultiTaskGradient."""
+    lib = load()
+    dev = margins_padded_flat.device
+    if margins_padded_flat.dtype != torch.float32:
+        raise NotImplementedError("multi-task GPU path carries f32 margins")
+    n = margins_padded_flat.numel() // kc
+    labels = labels.contiguous()
+    if labels.dtype != torch.float32:
+        labels = labels.to(torch.float32)
+    mask = _prep_mask(mask, dev)
+    sw = _prep_weights(sample_weight, dev)
+    if fold_id is not None:
+        fold_id = fold_id.to(device=dev, dtype=torch.int32).contiguous()
+        if fold_id.numel() != n:
+            raise ValueError("fold_id must be [n]")
+    if holdout is not None:
+        holdout = holdout.to(device=dev, dtype=torch.int32).contiguous()
+        if holdout.numel() != r:
+            raise ValueError("holdout must be [num_tasks]")
+    task_scale = task_scale.to(device=dev, dtype=torch.float32).contiguous()
+    if task_scale.numel() != r or labels.numel() != n:
+        raise ValueError("task_scale must be [num_tasks] and labels [n]")
+    M = (torch.empty(n * kc, dtype=torch.float32, device=dev)
+         if need_mult else None)
+    task_loss = torch.empty(r, dtype=torch.float64, device=dev)
+    loss_count = torch.empty(2, dtype=torch.float64, device=dev)
+    rc = lib.agd_multiplier_tasks(
+        _ptr(margins_padded_flat.contiguous()), _ptr(labels), _ptr(mask),
+        _ptr(sw), _ptr(fold_id), _ptr(holdout), _ptr(task_scale),
+        int(loss_type), int(bool(invert)), n, r, kc, _ptr(M), _ptr(task_loss),
+        _ptr(loss_count), _ptr(_tasks_ws(dev, kc)),
+        _stream(margins_padded_flat))
+    _check(rc)
+    return M, task_loss, loss_count
+
+
+def prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
+               lam: torch.Tensor, lam2: torch.Tensor
+               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``prox`` over the flat feature-major [d, R] block with task r's
+    (lam[r], lam2[r]); lam / lam2 are f64 [R] on w's device."""
+    lib = load()
+    r = lam.numel()
+    if lam2.numel() != r or w.numel() % r != 0:
+        raise ValueError("prox_tasks: weights must be [d * R] with lam, lam2 [R]")
+    lam = lam.to(device=w.device, dtype=torch.float64).contiguous()
+    lam2 = lam2.to(device=w.device, dtype=torch.float64).contiguous()
+    out = torch.empty_like(w)
+    reg = torch.zeros((), dtype=torch.float64, device=w.device)
+    rc = lib.agd_prox_tasks(kind, _ptr(w.contiguous()), _ptr(g.contiguous()),
+                            float(step), _ptr(lam), _ptr(lam2), r, _ptr(out),
+                            _ptr(reg), w.numel(), _VEC_DTYPE[w.dtype],
+                            _ptr(_red_ws(w.device)), _stream(w))
+    _check(rc)
+    return out, reg
 
 
 def dense_eval_multi_from_margins(
