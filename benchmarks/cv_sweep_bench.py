@@ -3,25 +3,30 @@
 one MI355X.
 
 One bf16 dense shard (262144 x 10240 by default), logistic loss, squared-L2
-regulariser, R = 15 tasks from 5 lambdas x 3 folds, timed two ways:
+regulariser, R = 15 tasks from 5 lambdas x 3 folds, timed three ways:
 
     batched      one run() of MultiTaskGradient over the [d, R] weight block:
-                 every stream of the shard serves all R tasks
+                 every stream of the shard serves all R tasks; margins
+                 tracked (two shard streams per step; track_margins=True,
+                 which a mixed sweep on a bf16 GPU shard needs to opt in)
+    untracked    the same batched run with track_margins=False (three
+                 streams per step) — mixed-lambda sweep only
     sequential   R single-task run() calls, one per (lambda, fold), each on
                  the WHOLE shard — not on the 2/3 of its rows a fold's
                  training set holds — so the figure is also reported scaled
                  by 2/3, the fair lower bound for a sequential sweep
 
-and under two sweeps: every lambda equal (plain SquaredL2Updater: margin
-tracking on, two shard streams per step) and mixed lambdas (PerTaskUpdater:
-untracked, three streams per step — the cost of the missing column-wise
-margin update).
+and under two sweeps: every lambda equal (plain SquaredL2Updater, the scalar
+fused margin update) and mixed lambdas (PerTaskUpdater, the per-column margin
+update k_at_margin_update_tasks). The untracked way is the mixed sweep before
+that kernel existed and what an L1 or elastic-net sweep still runs: the A/B
+of tracking comes from one alternating run.
 
 Each timed unit is one run() of --warmup + --steps iterations whose last
 --steps are bracketed by device synchronises; the sequential figure is the
-SUM of the R runs' ms/step. The two ways alternate, one of each per round,
-after one untimed round; the figures are the median and minimum over
---rounds rounds. Needs a GPU: there is no CPU fallback for a timing.
+SUM of the R runs' ms/step. The ways alternate, one of each per round, after
+one untimed round; the figures are the median and minimum over --rounds
+rounds. Needs a GPU: there is no CPU fallback for a timing.
 """
 
 import argparse
@@ -43,7 +48,8 @@ from sparkagd_amd.data import generate_dense_problem  # noqa: E402
 DEV = "cuda:0"
 
 
-def timed_run(shard, gradient, updater, reg, dim, warmup, steps):
+def timed_run(shard, gradient, updater, reg, dim, warmup, steps,
+              track_margins="auto"):
     """ms per step over the last ``steps`` of one run of warmup + steps
     iterations from zero weights."""
     w0 = torch.zeros(dim, device=DEV, dtype=torch.float32)
@@ -61,7 +67,8 @@ def timed_run(shard, gradient, updater, reg, dim, warmup, steps):
 
     _w, hist = run(shard, gradient, updater, 0.0, warmup + steps, reg, w0,
                    1.0, math.inf, 0.5, 0.9, True,
-                   loss_history_mode="backtrack", iteration_hook=hook)
+                   loss_history_mode="backtrack", iteration_hook=hook,
+                   track_margins=track_margins)
     if "t1" not in t or len(hist) != warmup + steps:
         raise RuntimeError("run stopped before the timed window closed")
     return (t["t1"] - t["t0"]) * 1e3 / steps
@@ -73,26 +80,36 @@ def sweep(shard, folds, n_folds, lams, warmup, steps, rounds):
     r = len(holdout)
     grad = MultiTaskGradient(LogisticGradient(), r, folds, holdout)
     l2 = SquaredL2Updater()
-    if len(set(task_lams)) == 1:
-        upd, reg = l2, task_lams[0]
-    else:
+    mixed = len(set(task_lams)) > 1
+    if mixed:
         upd, reg = PerTaskUpdater(l2, task_lams), 1.0
+    else:
+        upd, reg = l2, task_lams[0]
 
-    def batched():
-        return timed_run(shard, grad, upd, reg, shard.d * r, warmup, steps)
+    def batched(track_margins=True):
+        return timed_run(shard, grad, upd, reg, shard.d * r, warmup, steps,
+                         track_margins)
 
     def sequential():
         return sum(timed_run(shard, LogisticGradient(), l2, lam, shard.d,
                              warmup, steps) for lam in task_lams)
 
-    batched(), sequential()  # one untimed round: code objects, allocator
-    b, s = [], []
+    # one untimed round: code objects, allocator
+    batched(), (batched(False) if mixed else None), sequential()
+    b, u, s = [], [], []
     for _ in range(rounds):
         b.append(batched())
+        if mixed:
+            u.append(batched(False))
         s.append(sequential())
-    return {"tasks": r,
+    res = {}
+    if mixed:
+        res = {"untracked_ms_per_step": statistics.median(u),
+               "untracked_min": min(u), "untracked_rounds": u}
+    return {**res, "tasks": r,
             "batched_ms_per_step": statistics.median(b),
             "batched_min": min(b),
+            "batched_rounds": b,
             "sequential_sum_ms_per_step": statistics.median(s),
             "sequential_min": min(s),
             "sequential_two_thirds": statistics.median(s) * 2.0 / 3.0}
@@ -103,7 +120,12 @@ def report(title, res):
                  res["sequential_two_thirds"])
     print(title, flush=True)
     print(f"  batched     median {b:9.3f} ms/step  min {res['batched_min']:9.3f}"
-          f"   ({res['tasks']} tasks in one run)", flush=True)
+          f"   ({res['tasks']} tasks in one run, margins tracked)", flush=True)
+    if "untracked_ms_per_step" in res:
+        u = res["untracked_ms_per_step"]
+        print(f"  untracked   median {u:9.3f} ms/step  min {res['untracked_min']:9.3f}"
+              f"   (the same run, track_margins=False: {u / b:.2f}x the tracked)",
+              flush=True)
     print(f"  sequential  median {s:9.3f} ms/step  min {res['sequential_min']:9.3f}"
           f"   (sum of {res['tasks']} runs, each on the WHOLE shard)", flush=True)
     print(f"  sequential x 2/3   {s23:9.3f} ms/step"
@@ -144,11 +166,11 @@ def main():
         args.steps, args.rounds)
     report(f"equal lambda ({mid:g}): plain updater, margins tracked",
            out["equal_lambda_tracked"])
-    out["mixed_lambda_untracked"] = sweep(
+    out["mixed_lambda"] = sweep(
         shard, folds, args.folds, args.lambdas, args.warmup, args.steps,
         args.rounds)
-    report("mixed lambdas: PerTaskUpdater, untracked",
-           out["mixed_lambda_untracked"])
+    report("mixed lambdas: PerTaskUpdater, margins tracked per column",
+           out["mixed_lambda"])
     out["shard_packed_by_policy"] = bool(shard.is_packed)
     print("RESULT " + json.dumps(out), flush=True)
 

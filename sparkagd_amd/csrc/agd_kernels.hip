@@ -4319,3 +4319,120 @@ extern "C" int agd_prox_tasks(int kind, const void* w, const void* g,
   HIP_CHECK(hipGetLastError());
   return 0;
 }
+
+// 1 - step*lam in f64 as the host rounds it, product and difference
+// separately: contraction is off here because the _rn intrinsics are plain
+// operators to the compiler and would fuse into one fma.
+__device__ __forceinline__ double task_shrink(double step, double lam) {
+#pragma clang fp contract(off)
+  const double p = step * lam;
+  return 1.0 - p;
+}
+
+// One element of the AT margin update, with the roundings of
+// k_at_margin_update's vector body written out: from `pz*zo + pg*g` and
+// `(1-th)*xo + th*zn` the compiler forms there fma(pz, zo, pg*g) and
+// fma(1-th, xo, th*zn). Left to contraction the same spelling fuses
+// differently from kernel to kernel (it did here, element by element), so the
+// per-task kernel fixes that form instead of repeating the spelling.
+template <typename T>
+__device__ __forceinline__ void at_update_elem(T tpz, T tpg, T tom, T tth,
+                                               T zo, T xo, T gv, T& zn, T& xn) {
+#pragma clang fp contract(off)
+  const T pg_g = tpg * gv;
+  zn = fma(tpz, zo, pg_g);
+  const T th_z = tth * zn;
+  xn = fma(tom, xo, th_z);
+}
+
+// k_at_margin_update with a per-task shrink: the margins are the padded
+// [n, KC] flats, column c < R belongs to task c and
+//   zm'[:, c] = (1 - step*lam[c])*zm[:, c] - step*gm[:, c]
+//   xm'       = (1 - theta)*xm + theta*zm'
+// Pad columns c >= R of both outputs are stored as exact zeros whatever the
+// inputs hold there. pz_c = 1 - step*lam[c] is formed in f64 with the product
+// and the difference rounded separately (what the host computes for the
+// scalar kernel), then cast to T, and the elements round as the scalar
+// kernel's do (at_update_elem): an equal-lambda call without pads is bitwise
+// the scalar kernel. KC % 4 == 0, so a 16-B vector never straddles a row and
+// n*KC has no vector tail; the column of a thread's vector is carried along
+// the grid-stride loop as k_prox_tasks carries its task index, and the
+// coefficients are rebuilt only when it moves (never, when the grid stride is
+// a multiple of KC — every power-of-two KC). lam is an R-entry f64 device
+// vector read through the cache (guarded: nothing is read for a pad column),
+// so no LDS budget caps R.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_at_margin_update_tasks(
+    const T* __restrict__ zm_old, const T* __restrict__ xm_old,
+    const T* __restrict__ gm, double step, const double* __restrict__ lam,
+    double theta, ll n, int R, int KC, T* __restrict__ zm_new,
+    T* __restrict__ xm_new) {
+  constexpr int VE = 16 / sizeof(T);
+  const T tpg = (T)(-step), tth = (T)theta, tom = (T)(1.0 - theta);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const ll nv = n * KC / VE;
+  int c0 = (int)((gid * VE) % KC);
+  const int dc = (int)((stride * VE) % KC);
+  T tpz[VE];
+  bool live[VE];
+  auto coeffs = [&]() {
+#pragma unroll
+    for (int k = 0; k < VE; ++k) {
+      live[k] = c0 + k < R;
+      tpz[k] = live[k] ? (T)task_shrink(step, lam[c0 + k]) : (T)0;
+    }
+  };
+  coeffs();
+  for (ll i = gid; i < nv; i += stride) {
+    T zo[VE], xo[VE], gv[VE], zn[VE], xn[VE];
+    loadAcc<T, VE>(zm_old + i * VE, zo);
+    loadAcc<T, VE>(xm_old + i * VE, xo);
+    loadAcc<T, VE>(gm + i * VE, gv);
+#pragma unroll
+    for (int k = 0; k < VE; ++k) {
+      at_update_elem(tpz[k], tpg, tom, tth, zo[k], xo[k], gv[k], zn[k], xn[k]);
+      if (!live[k]) zn[k] = xn[k] = (T)0;
+    }
+    storeAcc<T, VE>(zm_new + i * VE, zn);
+    storeAcc<T, VE>(xm_new + i * VE, xn);
+    if (dc != 0) {
+      c0 += dc;
+      if (c0 >= KC) c0 -= KC;
+      coeffs();
+    }
+  }
+}
+
+// lam is f64[R] device; the margins are [n * kc] with kc % 4 == 0, R <= kc.
+extern "C" int agd_at_margin_update_tasks(
+    const void* zm_old, const void* xm_old, const void* gm, double step,
+    const void* lam, double theta, long long n, int R, int kc, int dtype,
+    void* zm_new, void* xm_new, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (kc < 4 || (kc & 3) || R < 1 || R > kc || n < 0 || lam == nullptr) {
+    snprintf(g_err, sizeof(g_err),
+             "at_margin_update_tasks: bad R %d / KC %d / n %lld or null lambdas",
+             R, kc, n);
+    return 2;
+  }
+  const int grid = grid_for(n * kc / (dtype == 2 ? 2 : 4) + 1, BLOCK);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_at_margin_update_tasks<float>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const float*)zm_old,
+                       (const float*)xm_old, (const float*)gm, step,
+                       (const double*)lam, theta, (ll)n, R, kc,
+                       (float*)zm_new, (float*)xm_new);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_at_margin_update_tasks<double>), dim3(grid),
+                       dim3(BLOCK), 0, s, (const double*)zm_old,
+                       (const double*)xm_old, (const double*)gm, step,
+                       (const double*)lam, theta, (ll)n, R, kc,
+                       (double*)zm_new, (double*)xm_new);
+  else {
+    snprintf(g_err, sizeof(g_err), "at_margin_update_tasks: bad dtype %d", dtype);
+    return 2;
+  }
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}

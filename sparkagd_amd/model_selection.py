@@ -88,9 +88,18 @@ def cross_validate(
     [n_local] is given. Dense and CSR shards, direct solver.
 
     The R tasks share one step size, θ sequence and restart test, so they
-    converge together, paced by the slowest; a sweep whose lambdas are all
-    equal keeps margin tracking (two shard streams per step), a mixed sweep
-    runs untracked (three).
+    converge together, paced by the slowest. With a simple or squared-L2
+    updater the run tracks its margins (two shard streams per step), whether
+    the lambdas are equal or mixed: a mixed sweep updates them with one shrink
+    per column. ``config.track_margins=False`` keeps the untracked path
+    (three streams with ``loss_history_mode="backtrack"``, four at the
+    defaults), which is also what an L1 or elastic-net sweep runs. One
+    exception: a MIXED sweep on a bf16 dense shard on the GPU is tracked only
+    with ``config.track_margins=True``. Its margins GEMM rounds the weights
+    to bf16, tracked margins then carry that rounding of every increment,
+    and a column whose ``step * lambda`` passes 1 does not damp it: with
+    lambdas spread over decades under one shared step, a tracked run was
+    seen to pick another ``best_lambda`` than the f64 run.
     """
     from .optimizer import run
 

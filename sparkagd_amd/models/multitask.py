@@ -21,7 +21,8 @@ from typing import Optional, Sequence
 import torch
 
 from .gradient import Gradient
-from .updater import ElasticNetUpdater, FreeTailUpdater, Updater
+from .updater import (ElasticNetUpdater, FreeTailUpdater, SimpleUpdater,
+                      SquaredL2Updater, Updater)
 
 
 class MultiTaskGradient(Gradient):
@@ -150,6 +151,16 @@ class MultiTaskGradient(Gradient):
             self._dev_cache[device] = t
         return t
 
+    def rounds_margin_weights(self, shard) -> bool:
+        """True when the training ``margins`` pass rounds its weight operand:
+        a bf16 dense shard on the GPU runs it as a bf16 x bf16 GEMM. Margins
+        tracked through such a pass carry 2^-9 of every INCREMENT of z, not
+        of z itself; where a column's shrink 1 - step*lambda leaves (-1, 1)
+        that error is not damped, and a mixed sweep shares one step among
+        columns with very different lambdas."""
+        return (shard.kind == "dense" and shard.features.is_cuda
+                and shard.features.dtype == torch.bfloat16)
+
     def margins(self, shard, v, scoring=False):
         """Padded margins [n*KC] of the weight block ``v``. ``scoring=True``
         keeps the f32 weights of a bf16 dense shard (split into two bf16
@@ -217,10 +228,15 @@ class PerTaskUpdater(Updater):
     (``ElasticNetUpdater`` splits it by its ``l1_ratio``); the regularisation
     value is the sum over the tasks.
 
-    ``AFFINE_PROX`` is False — a mixed-lambda run is untracked (the fused
-    margin update takes one (pz, pg) pair, not one per column). When every
-    lambda is equal use the plain updater: margin tracking is then on, as for
-    softmax."""
+    ``AFFINE_PROX`` stays False: that flag promises ONE (pz, pg) pair for the
+    whole margin vector (the scalar fused update, the Gram solver), and here
+    the shrink differs per column. A ``SimpleUpdater`` or ``SquaredL2Updater``
+    base is still affine column by column, which the instance attribute
+    ``COLUMN_AFFINE_PROX`` says: the optimizer then tracks the margins of a
+    ``MultiTaskGradient`` run through ``prox_margins_tasks`` (two shard
+    streams per step, as with one lambda; on a bf16 dense GPU shard only with
+    ``track_margins=True``, see ``MultiTaskGradient.rounds_margin_weights``).
+    L1 and elastic-net bases are not affine and run untracked."""
 
     AFFINE_PROX = False
 
@@ -234,6 +250,8 @@ class PerTaskUpdater(Updater):
         self.PROX_KIND = base.PROX_KIND
         self.lambdas = lam
         self.num_tasks = lam.numel()
+        #: the prox is affine in (w, g) column by column (see the class doc)
+        self.COLUMN_AFFINE_PROX = type(base) in (SimpleUpdater, SquaredL2Updater)
         self._cache = {}
 
     def _lams(self, reg_param: float, device):
@@ -245,6 +263,10 @@ class PerTaskUpdater(Updater):
             eff = self.lambdas * float(reg_param)
             if isinstance(self.base, ElasticNetUpdater):
                 lam, lam2 = self.base.l1_ratio * eff, (1.0 - self.base.l1_ratio) * eff
+            elif isinstance(self.base, SimpleUpdater):
+                # no regulariser: the prox ignores lam, the margin update
+                # must see zeros
+                lam, lam2 = torch.zeros_like(eff), torch.zeros_like(eff)
             else:
                 lam, lam2 = eff, torch.zeros_like(eff)
             t = (lam.to(device), lam2.to(device))
@@ -261,6 +283,20 @@ class PerTaskUpdater(Updater):
         lam, lam2 = self._lams(reg_param, weights_old.device)
         return mt.prox_tasks(self.PROX_KIND, weights_old, gradient,
                              step_size / math.sqrt(iter), lam, lam2)
+
+    def prox_margins_tasks(self, zm_old, xm_old, gm, step, reg_param, theta):
+        """(zm', xm') of the padded [n*KC] margins after the prox step
+        ``compute`` takes at ``step`` and the AT interpolation at ``theta``;
+        only valid when ``COLUMN_AFFINE_PROX``. The lambdas are the cached
+        device vector of ``compute``: the step copies nothing to the device."""
+        from ..ops import multitask as mt
+
+        if not self.COLUMN_AFFINE_PROX:
+            raise NotImplementedError(
+                f"PerTaskUpdater({type(self.base).__name__}) has no affine prox")
+        lam, _ = self._lams(reg_param, zm_old.device)
+        return mt.at_margin_update_tasks(zm_old, xm_old, gm, step, lam, theta,
+                                         self.num_tasks)
 
     def reg_value(self, weights, reg_param):
         return self.compute(weights, torch.zeros_like(weights), 0.0, 1,

@@ -147,6 +147,9 @@ def load() -> ctypes.CDLL:
                                          P, P, P, P, P]
     lib.agd_prox_tasks.restype = I
     lib.agd_prox_tasks.argtypes = [I, P, P, D, P, P, I, P, P, LL, I, P, P]
+    lib.agd_at_margin_update_tasks.restype = I
+    lib.agd_at_margin_update_tasks.argtypes = [P, P, P, D, P, D, LL, I, I, I,
+                                               P, P, P]
 
     _lib = lib
     return lib
@@ -721,6 +724,34 @@ def prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
                             _ptr(_red_ws(w.device)), _stream(w))
     _check(rc)
     return out, reg
+
+
+def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
+                           gm: torch.Tensor, step: float, lam: torch.Tensor,
+                           theta: float, num_tasks: int, kc: int):
+    """(zm_new, xm_new) of the padded [n*kc] margins with task r's shrink
+    ``1 - step*lam[r]`` (k_at_margin_update_tasks); pad columns come out as
+    exact zeros. lam is f64 [R]: already on the device it is used as it is
+    (no copy, no synchronisation)."""
+    lib = load()
+    total = zm_old.numel()
+    if total % kc != 0 or xm_old.numel() != total or gm.numel() != total:
+        raise ValueError("at_margin_update_tasks: margins must be three "
+                         f"[n * {kc}] flats")
+    if xm_old.dtype != zm_old.dtype or gm.dtype != zm_old.dtype:
+        raise TypeError("at_margin_update_tasks: margins must share one dtype")
+    if lam.numel() != num_tasks:
+        raise ValueError("at_margin_update_tasks: lam must be [num_tasks]")
+    lam = lam.to(device=zm_old.device, dtype=torch.float64).contiguous()
+    zm_new = torch.empty_like(zm_old)
+    xm_new = torch.empty_like(xm_old)
+    rc = lib.agd_at_margin_update_tasks(
+        _ptr(zm_old.contiguous()), _ptr(xm_old.contiguous()),
+        _ptr(gm.contiguous()), float(step), _ptr(lam), float(theta),
+        total // kc, int(num_tasks), int(kc), _VEC_DTYPE[zm_old.dtype],
+        _ptr(zm_new), _ptr(xm_new), _stream(zm_old))
+    _check(rc)
+    return zm_new, xm_new
 
 
 def dense_eval_multi_from_margins(

@@ -114,6 +114,32 @@ def ref_prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
     return w_new.reshape(-1), reg
 
 
+def ref_at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
+                               gm: torch.Tensor, step: float,
+                               lam: torch.Tensor, theta: float,
+                               num_tasks: int
+                               ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """AT margin update of the padded [n*KC] flats with a shrink per task:
+
+        zm'[:, r] = (1 - step*lam[r])*zm[:, r] - step*gm[:, r]
+        xm'       = (1 - theta)*xm + theta*zm'
+
+    for r < num_tasks, the coefficient formed in f64 and cast to the margins'
+    dtype. Pad columns of both outputs are exact zeros and are never read."""
+    kc = padded_k(num_tasks)
+    n = zm_old.numel() // kc
+    dt = zm_old.dtype
+    pz = (1.0 - step * lam.to(device=zm_old.device, dtype=torch.float64)).to(dt)
+    live = slice(0, num_tasks)
+    zm_new = torch.zeros((n, kc), dtype=dt, device=zm_old.device)
+    xm_new = torch.zeros((n, kc), dtype=dt, device=zm_old.device)
+    zn = (pz.unsqueeze(0) * zm_old.reshape(n, kc)[:, live]
+          - step * gm.reshape(n, kc)[:, live])
+    zm_new[:, live] = zn
+    xm_new[:, live] = (1.0 - theta) * xm_old.reshape(n, kc)[:, live] + theta * zn
+    return zm_new.reshape(-1), xm_new.reshape(-1)
+
+
 # --- dispatch (GPU -> HIP kernels via hiplib; CPU -> oracle) ---
 
 def multiplier_tasks(
@@ -159,6 +185,26 @@ def prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
 
         return hiplib.prox_tasks(kind, w, g, step, lam, lam2)
     return ref_prox_tasks(kind, w, g, step, lam, lam2)
+
+
+def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
+                           gm: torch.Tensor, step: float, lam: torch.Tensor,
+                           theta: float, num_tasks: int
+                           ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused AT margin update of a multi-task run whose prox is affine per
+    column (simple: ``lam`` zeros; squared L2): (zm', xm') from the padded
+    [n*KC] margins of z, x and the gradient in one pass; ``lam`` is [R]
+    (f64). Pad columns of the outputs are exact zeros."""
+    if lam.numel() != num_tasks:
+        raise ValueError(f"lam has {lam.numel()} entries for {num_tasks} tasks")
+    if _use_hip(zm_old):
+        from . import hiplib
+
+        return hiplib.at_margin_update_tasks(zm_old, xm_old, gm, step, lam,
+                                             theta, num_tasks,
+                                             padded_k(num_tasks))
+    return ref_at_margin_update_tasks(zm_old, xm_old, gm, step, lam, theta,
+                                      num_tasks)
 
 
 def dense_margins_scoring(features: torch.Tensor, wflat: torch.Tensor,

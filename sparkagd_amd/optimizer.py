@@ -138,7 +138,13 @@ def run(
     rejected trial costs 2 instead of 3; loss-only f_x checks cost ZERO
     passes). The math is identical up to fp accumulation order;
     ``margin_refresh_every`` > 0 recomputes the tracked margins from the
-    weight vectors every k iterations to bound drift. Disabled automatically
+    weight vectors every k iterations to bound drift. A ``PerTaskUpdater``
+    over a Simple/SquaredL2 base on a ``MultiTaskGradient`` with the same
+    number of tasks is tracked as well: its prox is affine column by column
+    of the [n, KC] margins (``COLUMN_AFFINE_PROX``). On a bf16 dense shard
+    on the GPU, whose margins GEMM rounds the weights to bf16, that
+    per-column tracking is on only with ``track_margins=True``: ``"auto"``
+    keeps such a run untracked. Disabled automatically
     for non-affine updaters (L1) and when ``resume_from``/bitwise
     reproducibility against the non-tracking path is required
     (``track_margins=False``).
@@ -243,8 +249,21 @@ def run(
         return (loss_sum / count if count > 0 else float("nan")), grad_sum, count
 
     # Margin-state tracking eligibility (see docstring).
-    tracking = bool(track_margins) and getattr(updater, "AFFINE_PROX", False) \
+    # A PerTaskUpdater over an affine base is affine per COLUMN of a
+    # multi-task run's [n, KC] margins: tracked too, through its own fused
+    # update (one shrink per task).
+    column_affine = bool(getattr(updater, "COLUMN_AFFINE_PROX", False)) \
+        and getattr(gradient, "IS_MULTITASK", False) \
+        and getattr(gradient, "num_tasks", None) == getattr(updater, "num_tasks", -1)
+    if column_affine and track_margins == "auto" \
+            and gradient.rounds_margin_weights(data):
+        # bf16 GEMM margins: the default stays untracked (see
+        # MultiTaskGradient.rounds_margin_weights); track_margins=True opts in
+        column_affine = False
+    tracking = bool(track_margins) \
+        and (getattr(updater, "AFFINE_PROX", False) or column_affine) \
         and hasattr(data, "margins") and hasattr(data, "eval_from_margins")
+    column_tracking = tracking and not getattr(updater, "AFFINE_PROX", False)
     xm = zm = None
     if tracking:
         xm = gradient.margins(data, x)
@@ -286,11 +305,18 @@ def run(
             x = ops.axpby(1.0 - theta, x_old, theta, z)
             if tracking:
                 gm = gradient.margins(data, g_y)  # the only other data pass
-                try:
-                    pz, pg = updater.prox_margin_coeffs(step, reg_param)
-                except NotImplementedError:
-                    pz = None
-                if pz is not None:
+                pz = None
+                if not column_tracking:
+                    try:
+                        pz, pg = updater.prox_margin_coeffs(step, reg_param)
+                    except NotImplementedError:
+                        pass
+                if column_tracking:
+                    # zm' and xm' in one pass with a shrink per task
+                    # (k_at_margin_update_tasks)
+                    zm, xm = updater.prox_margins_tasks(
+                        zm_old, xm_old, gm, step, reg_param, theta)
+                elif pz is not None:
                     # fused: zm' and xm' in one pass (k_at_margin_update) —
                     # one launch + one fewer read stream than the
                     # prox-margins + axpby pair; identical algebra
