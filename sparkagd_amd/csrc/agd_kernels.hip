@@ -348,13 +348,125 @@ __device__ __forceinline__ void storeAcc(TACC* __restrict__ p, const TACC (&v)[W
 
 #define MARGIN_ROWS 4   // R: rows per wave (w-load amortization)
 #define MARGIN_ROWS_FP8 8  // 1-byte elements: R=4 would make w-bytes ~ A-bytes
+// Packed groups (1.5 B per element). Slab planning keeps MARGIN_ROWS; only
+// the task count and the tail row group follow this R.
+#define MARGIN_ROWS_PK 8
+// Packed sweeps per loop iteration: 2 issues the loads of groups l and l+64
+// of all R rows before the first decode.
+#define MARGIN_SWEEPS_PK 2
+
+template <typename TA>
+constexpr int margin_rows() {
+  return IsPacked<TA>::value ? MARGIN_ROWS_PK
+         : (sizeof(TA) == 1) ? MARGIN_ROWS_FP8
+                             : MARGIN_ROWS;
+}
+
+// a * b + c with the product rounded before the sum (never contracted).
+__device__ __forceinline__ float mul_add_2r(float a, float b, float c) {
+#pragma clang fp contract(off)
+  return a * b + c;
+}
+
+// The rounding of row j of a row group in the raw kernel's compiled sweep:
+// of every four full rows it fuses the multiply-add of the first two and
+// rounds the product separately for the last two, and it fuses all rows of
+// a tail group (< MARGIN_ROWS rows). The packed sweep spells that choice
+// out, row by row, so that its sums are the raw kernel's bit for bit
+// whatever its own R and loop shape are.
+__device__ __forceinline__ bool pk_row_fused(ll r, ll n) {
+  return (r & ~(ll)(MARGIN_ROWS - 1)) + MARGIN_ROWS > n ||
+         (r & (MARGIN_ROWS - 1)) < MARGIN_ROWS / 2;
+}
+
+// acc += <decoded group v, wv> in ascending k, one rounding per term if
+// fused, two otherwise.
+__device__ __forceinline__ void pk_group_madd(const pk_u32x3 v,
+                                              const float (&wv)[8], float& acc,
+                                              bool fused, unsigned lut_lo,
+                                              unsigned lut_hi) {
+  unsigned bits[8];
+  pk_decode_bits(v, bits, lut_lo, lut_hi);
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const float a = __uint_as_float(bits[k]);
+    acc = fused ? __builtin_fmaf(a, wv[k], acc) : mul_add_2r(a, wv[k], acc);
+  }
+}
+
+// One (row-group, column-slab) task of the packed margins pass: rows
+// r0 .. r0 + nr - 1, this lane's groups of columns [c, c_hi) at a stride of
+// one wave sweep (64 groups, 768 B per row).
+template <int R, bool NT>
+__device__ __forceinline__ void pk_margin_rows(
+    const pk12* __restrict__ A, const float* __restrict__ w, ll r0, int nr,
+    ll n, ll d, ll c, ll c_hi, float (&acc)[R], unsigned lut_lo,
+    unsigned lut_hi) {
+  static_assert(R % MARGIN_ROWS == 0, "row groups are whole raw row groups");
+  constexpr ll SW = (ll)WAVE * 8;
+  if (nr == R) {  // full row group (hot path): r0 % MARGIN_ROWS == 0
+    if constexpr (MARGIN_SWEEPS_PK == 2) {
+      // two sweeps per iteration: 2R loads in flight per lane and 1536
+      // contiguous bytes per row; each row still adds group l, then group
+      // l + 64, so every lane's sum keeps the order of the loop below
+      for (; c + SW + 8 <= c_hi; c += 2 * SW) {
+        pk_u32x3 v0[R], v1[R];
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          const pk12* p = elem_at<pk12>(A, r0 + j, d, c);
+          const pk_u32x3* p0 = (const pk_u32x3*)p;
+          const pk_u32x3* p1 = (const pk_u32x3*)(p + WAVE);
+          v0[j] = NT ? __builtin_nontemporal_load(p0) : *p0;
+          v1[j] = NT ? __builtin_nontemporal_load(p1) : *p1;
+        }
+        float wv0[8], wv1[8];
+        loadAcc<float, 8>(w + c, wv0);
+        loadAcc<float, 8>(w + c + SW, wv1);
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+          pk_group_madd(v0[j], wv0, acc[j],
+                        (j & (MARGIN_ROWS - 1)) < MARGIN_ROWS / 2, lut_lo,
+                        lut_hi);
+#pragma unroll
+        for (int j = 0; j < R; ++j)
+          pk_group_madd(v1[j], wv1, acc[j],
+                        (j & (MARGIN_ROWS - 1)) < MARGIN_ROWS / 2, lut_lo,
+                        lut_hi);
+      }
+    }
+    for (; c + 8 <= c_hi; c += SW) {
+      pk_u32x3 v[R];
+#pragma unroll
+      for (int j = 0; j < R; ++j) {
+        const pk_u32x3* p = (const pk_u32x3*)elem_at<pk12>(A, r0 + j, d, c);
+        v[j] = NT ? __builtin_nontemporal_load(p) : *p;
+      }
+      float wv[8];
+      loadAcc<float, 8>(w + c, wv);
+#pragma unroll
+      for (int j = 0; j < R; ++j)
+        pk_group_madd(v[j], wv, acc[j],
+                      (j & (MARGIN_ROWS - 1)) < MARGIN_ROWS / 2, lut_lo,
+                      lut_hi);
+    }
+  } else {  // tail row group: whole groups, same k order
+    for (; c < c_hi; c += SW) {
+      float wv[8];
+      loadAcc<float, 8>(w + c, wv);
+      for (int j = 0; j < nr; ++j) {
+        const pk_u32x3 v = *(const pk_u32x3*)elem_at<pk12>(A, r0 + j, d, c);
+        pk_group_madd(v, wv, acc[j], pk_row_fused(r0 + j, n), lut_lo, lut_hi);
+      }
+    }
+  }
+}
 
 template <typename TA, typename TACC, int W, bool NT>
 __global__ __launch_bounds__(BLOCK) void k_dense_margins(
     const TA* __restrict__ A, const TACC* __restrict__ w, ll n, ll d,
     ll slab_w, int n_slabs, TACC* __restrict__ part, unsigned lut_lo,
     unsigned lut_hi) {
-  constexpr int R = (sizeof(TA) == 1) ? MARGIN_ROWS_FP8 : MARGIN_ROWS;
+  constexpr int R = margin_rows<TA>();
   constexpr bool PK = IsPacked<TA>::value;  // no column tails: d % 8 == 0
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
@@ -373,7 +485,9 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
 #pragma unroll
     for (int j = 0; j < R; ++j) acc[j] = (TACC)0;
     ll c = c_lo + (ll)lane * W;
-    if (nr == R) {  // full row group (hot path)
+    if constexpr (PK) {
+      pk_margin_rows<R, NT>(A, w, r0, nr, n, d, c, c_hi, acc, lut_lo, lut_hi);
+    } else if (nr == R) {  // full row group (hot path)
       for (; c + W <= c_hi; c += (ll)WAVE * W) {
         TACC wv[W];
         loadAcc<TACC, W>(w + c, wv);
@@ -386,7 +500,7 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
           for (int k = 0; k < W; ++k) acc[j] += v[k] * wv[k];
         }
       }
-      if constexpr (!PK) if (c < c_hi) {
+      if (c < c_hi) {
 #pragma unroll
         for (int k = 0; k < W; ++k)
           if (c + k < c_hi) {
@@ -398,16 +512,6 @@ __global__ __launch_bounds__(BLOCK) void k_dense_margins(
               acc[j] += v[0] * wk;
             }
           }
-      }
-    } else if constexpr (PK) {  // tail row group: whole groups, same k order
-      for (c = c_lo + (ll)lane * W; c < c_hi; c += (ll)WAVE * W) {
-        for (int j = 0; j < nr; ++j) {
-          TACC v[W];
-          loadA<TA, TACC, W, false>(elem_at<TA>(A, r0 + j, d, c), v, lut_lo,
-                                    lut_hi);
-#pragma unroll
-          for (int k = 0; k < W; ++k) acc[j] += v[k] * w[c + k];
-        }
       }
     } else {  // tail row group (at most one per slab; plain W stride)
       for (c = c_lo + (ll)lane * W; c < c_hi; c += (ll)WAVE * W) {
@@ -1726,58 +1830,79 @@ __device__ __forceinline__ int pk_slot(unsigned h, unsigned lut_lo,
   return k;
 }
 
+// 64-bit escape words of one packed row: bit l of word i says that group
+// 64 i + l of the row holds at least one escape.
+__host__ __device__ __forceinline__ ll pk_row_words(ll d) {
+  return (pk_row_groups(d) + WAVE - 1) / WAVE;
+}
+
+// 8-bit escape mask of one raw group (bit k: element k's high-byte magnitude
+// is not in the table).
+__device__ __forceinline__ unsigned pk_escape_mask(
+    const __attribute__((ext_vector_type(8))) unsigned short v,
+    unsigned lut_lo, unsigned lut_hi) {
+  unsigned mask = 0u;
+#pragma unroll
+  for (int k = 0; k < 8; ++k)
+    if (pk_slot(((unsigned)v[k] >> 8) & 0x7fu, lut_lo, lut_hi) < 0)
+      mask |= 1u << k;
+  return mask;
+}
+
 // Encode: one block per row (grid-stride over rows), one thread per 8-element
-// group. An escape (high-byte magnitude not in the table) is stored as the
-// all-zero code, which decodes to +0.0f because table slot 0 is 0x00; the
-// row's escape count goes to esc_count[r] and the group's 8-bit escape mask
-// to flags[r * row_groups + g] (zero in the row padding), so that collecting
-// the escapes does not have to read the shard again.
+// group. A wave reads 1024 and writes 768 contiguous bytes per sweep, both on
+// whole 128-B lines when d % 64 == 0 (the row padding keeps the stores there
+// for any d). An escape (high-byte magnitude not in the table) is stored as
+// the all-zero code, which decodes to +0.0f because table slot 0 is 0x00;
+// the row's escape count goes to esc_count[r]. Each wave sweep leaves one
+// 64-bit ballot word, bit l = "lane l's group has an escape" (zero in the
+// row padding), written by one lane: collecting the escapes then reads 1/64
+// byte per element and only the flagged groups of the shard again.
 __global__ __launch_bounds__(BLOCK) void k_dense_pack_encode(
     const ubf16* __restrict__ A, ll n, ll d, unsigned lut_lo, unsigned lut_hi,
     pk12* __restrict__ P, int* __restrict__ esc_count,
-    unsigned char* __restrict__ flags) {
+    unsigned long long* __restrict__ words) {
   using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
   typedef unsigned int u32x3 __attribute__((ext_vector_type(3), aligned(4)));
   __shared__ int wsum[WAVES_PER_BLOCK];
+  const int lane = threadIdx.x & (WAVE - 1);
   const ll gpr = d >> 3;
   const ll gs = pk_row_groups(d);
+  const ll wpr = pk_row_words(d);
   for (ll r = blockIdx.x; r < n; r += gridDim.x) {
     int esc = 0;
     for (ll g = threadIdx.x; g < gs; g += BLOCK) {
-      if (g >= gpr) {  // row padding: zero groups
-        u32x3 o;
-        o[0] = o[1] = o[2] = 0u;
-        *(u32x3*)(P + r * gs + g) = o;
-        flags[r * gs + g] = 0;
-        continue;
-      }
-      const u16x8 v = *(const u16x8*)(A + r * d + g * 8);
       unsigned lo[2] = {0u, 0u}, z = 0u, mask = 0u;
+      if (g < gpr) {  // else row padding: a zero group
+        const u16x8 v = *(const u16x8*)(A + r * d + g * 8);
 #pragma unroll
-      for (int k = 0; k < 8; ++k) {
-        const unsigned u = v[k];
-        const int slot = pk_slot((u >> 8) & 0x7fu, lut_lo, lut_hi);
-        unsigned code = 0u, lowb = 0u;
-        if (slot >= 0) {
-          code = ((u >> 15) << 3) | (unsigned)slot;
-          lowb = u & 0xffu;
-        } else {
-          ++esc;
-          mask |= 1u << k;
+        for (int k = 0; k < 8; ++k) {
+          const unsigned u = v[k];
+          const int slot = pk_slot((u >> 8) & 0x7fu, lut_lo, lut_hi);
+          unsigned code = 0u, lowb = 0u;
+          if (slot >= 0) {
+            code = ((u >> 15) << 3) | (unsigned)slot;
+            lowb = u & 0xffu;
+          } else {
+            mask |= 1u << k;
+          }
+          lo[k >> 2] |= lowb << (8 * (k & 3));
+          z |= code << (8 * (k & 3) + 4 * (k >> 2));
         }
-        lo[k >> 2] |= lowb << (8 * (k & 3));
-        z |= code << (8 * (k & 3) + 4 * (k >> 2));
       }
       u32x3 o;
       o[0] = lo[0];
       o[1] = lo[1];
       o[2] = z;
       *(u32x3*)(P + r * gs + g) = o;
-      flags[r * gs + g] = (unsigned char)mask;
+      esc += __popc(mask);
+      // lanes past the row's end are not in the ballot: their bits are zero
+      const unsigned long long word = __ballot(mask != 0u);
+      if (lane == 0) words[r * wpr + g / WAVE] = word;
     }
     esc = wave_reduce_sum(esc);
     __syncthreads();  // wsum reuse across rows
-    if ((threadIdx.x & (WAVE - 1)) == 0) wsum[threadIdx.x / WAVE] = esc;
+    if (lane == 0) wsum[threadIdx.x / WAVE] = esc;
     __syncthreads();
     if (threadIdx.x == 0) {
       int t = 0;
@@ -1788,28 +1913,38 @@ __global__ __launch_bounds__(BLOCK) void k_dense_pack_encode(
   }
 }
 
-// Escape coordinates in row order from the encode pass's flags: one wave per
-// row, 256 groups per sweep (4 flag bytes per lane; the padded row stride is
-// a multiple of 32 groups, so the dword loads are aligned and in bounds). A
-// wave prefix sum places each lane's escapes after those of lower lanes, so
-// col[] ascends inside a row. rowptr is the exclusive scan of esc_count.
+// Escape coordinates in row order from the encode pass's words: one wave per
+// row, one word (64 groups) per lane and sweep. A lane walks the set bits of
+// its word in ascending order, reads those groups of A again and rebuilds
+// their element masks; popcounts give the lane's escapes, and a wave prefix
+// sum places them after those of lower lanes, so col[] ascends inside a row.
+// rowptr is the exclusive scan of esc_count.
 __global__ __launch_bounds__(BLOCK) void k_dense_pack_escapes(
-    const ubf16* __restrict__ A, ll n, ll d,
-    const unsigned char* __restrict__ flags, const int* __restrict__ rowptr,
-    int* __restrict__ col, float* __restrict__ val) {
+    const ubf16* __restrict__ A, ll n, ll d, unsigned lut_lo, unsigned lut_hi,
+    const unsigned long long* __restrict__ words,
+    const int* __restrict__ rowptr, int* __restrict__ col,
+    float* __restrict__ val) {
+  using u16x8 = __attribute__((ext_vector_type(8))) unsigned short;
   const int lane = threadIdx.x & (WAVE - 1);
   const ll wave_gid = (ll)blockIdx.x * WAVES_PER_BLOCK + threadIdx.x / WAVE;
   const ll n_waves = (ll)gridDim.x * WAVES_PER_BLOCK;
-  const ll gs = pk_row_groups(d);
+  const ll gpr = d >> 3;
+  const ll wpr = pk_row_words(d);
   for (ll r = wave_gid; r < n; r += n_waves) {
     int base = rowptr[r];
     const int end = rowptr[r + 1];
     if (base == end) continue;  // wave-uniform
-    for (ll g0 = 0; g0 < gs; g0 += 4 * WAVE) {
-      const ll g = g0 + 4 * lane;
-      unsigned mask = 0u;  // byte j: escape mask of group g + j
-      if (g < gs) mask = *(const unsigned int*)(flags + r * gs + g);
-      const int cnt = __popc(mask);
+    for (ll w0 = 0; w0 < wpr; w0 += WAVE) {
+      const ll wi = w0 + lane;
+      const unsigned long long word = (wi < wpr) ? words[r * wpr + wi] : 0ull;
+      if (__ballot(word != 0ull) == 0ull) continue;  // wave-uniform
+      int cnt = 0;
+      for (unsigned long long t = word; t; t &= t - 1ull) {
+        const ll g = wi * WAVE + (__ffsll((long long)t) - 1);
+        if (g < gpr)  // keeps the load inside the row
+          cnt += __popc(pk_escape_mask(*(const u16x8*)(A + r * d + g * 8),
+                                       lut_lo, lut_hi));
+      }
       int incl = cnt;
 #pragma unroll
       for (int off = 1; off < WAVE; off <<= 1) {
@@ -1818,15 +1953,20 @@ __global__ __launch_bounds__(BLOCK) void k_dense_pack_escapes(
       }
       const int total = __shfl(incl, WAVE - 1, WAVE);
       int pos = base + incl - cnt;
-      while (mask) {  // ascending bit = ascending column
-        const int b = __ffs((int)mask) - 1;
-        mask &= mask - 1u;
-        const ll c = g * 8 + b;
-        if (pos < end && c < d) {  // the bounds keep loads and stores inside
-          col[pos] = (int)c;
-          val[pos] = bf2f(A[r * d + c]);
+      for (unsigned long long t = word; t; t &= t - 1ull) {
+        const ll g = wi * WAVE + (__ffsll((long long)t) - 1);
+        if (g >= gpr) continue;
+        const u16x8 v = *(const u16x8*)(A + r * d + g * 8);
+        unsigned mask = pk_escape_mask(v, lut_lo, lut_hi);
+        while (mask) {  // ascending bit = ascending column
+          const int b = __ffs((int)mask) - 1;
+          mask &= mask - 1u;
+          if (pos < end) {  // keeps the stores inside the lists
+            col[pos] = (int)(g * 8 + b);
+            val[pos] = bf2f(A[r * d + g * 8 + b]);
+          }
+          ++pos;
         }
-        ++pos;
       }
       base += total;
     }
@@ -2059,7 +2199,7 @@ static int dense_eval_t(const void* A, const float* labels,
                        stream, (const ubf16*)A, (const float*)w, n, d, slab_w,
                        n_slabs, (float*)margins);
   } else {
-    const int R = (sizeof(TA) == 1) ? MARGIN_ROWS_FP8 : MARGIN_ROWS;
+    const int R = margin_rows<TA>();
     const ll tasks = ((n + R - 1) / R) * n_slabs;
     const int grid = grid_for(tasks, WAVES_PER_BLOCK);
     if (nt_loads)
@@ -2204,33 +2344,39 @@ extern "C" long long agd_dense_pack_row_bytes(long long d) {
   return pk_row_groups(d) * 12;
 }
 
+// Escape words of one packed row (one 64-bit word per 64 groups).
+extern "C" long long agd_dense_pack_row_words(long long d) {
+  return pk_row_words(d);
+}
+
 // packed [n, agd_dense_pack_row_bytes(d)] bytes; esc_count [n] int32;
-// flags [n, agd_dense_pack_row_bytes(d) / 12] bytes.
+// words [n, agd_dense_pack_row_words(d)] 64-bit.
 extern "C" int agd_dense_pack_encode(const void* A, long long n, long long d,
                                      unsigned lut_lo, unsigned lut_hi,
                                      void* packed, void* esc_count,
-                                     void* flags, void* stream) {
+                                     void* words, void* stream) {
   if (!pack_shape_ok("agd_dense_pack_encode", A, n, d)) return 2;
   if (!pack_lut_ok("agd_dense_pack_encode", lut_lo)) return 2;
   const int grid = grid_for(n, 1);
   hipLaunchKernelGGL(k_dense_pack_encode, dim3(grid), dim3(BLOCK), 0,
                      (hipStream_t)stream, (const ubf16*)A, (ll)n, (ll)d, lut_lo,
                      lut_hi, (pk12*)packed, (int*)esc_count,
-                     (unsigned char*)flags);
+                     (unsigned long long*)words);
   HIP_CHECK(hipGetLastError());
   return 0;
 }
 
 // rowptr [n+1] int32 = exclusive scan of esc_count; col/val sized rowptr[n].
 extern "C" int agd_dense_pack_escapes(const void* A, long long n, long long d,
-                                      const void* flags, const void* rowptr,
+                                      unsigned lut_lo, unsigned lut_hi,
+                                      const void* words, const void* rowptr,
                                       void* col, void* val, void* stream) {
   if (!pack_shape_ok("agd_dense_pack_escapes", A, n, d)) return 2;
   const int grid = grid_for(n, WAVES_PER_BLOCK);
   hipLaunchKernelGGL(k_dense_pack_escapes, dim3(grid), dim3(BLOCK), 0,
                      (hipStream_t)stream, (const ubf16*)A, (ll)n, (ll)d,
-                     (const unsigned char*)flags, (const int*)rowptr, (int*)col,
-                     (float*)val);
+                     lut_lo, lut_hi, (const unsigned long long*)words,
+                     (const int*)rowptr, (int*)col, (float*)val);
   HIP_CHECK(hipGetLastError());
   return 0;
 }

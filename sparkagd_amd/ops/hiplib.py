@@ -64,7 +64,9 @@ def load() -> ctypes.CDLL:
     lib.agd_dense_pack_encode.restype = I
     lib.agd_dense_pack_encode.argtypes = [P, LL, LL, U, U, P, P, P, P]
     lib.agd_dense_pack_escapes.restype = I
-    lib.agd_dense_pack_escapes.argtypes = [P, LL, LL, P, P, P, P, P]
+    lib.agd_dense_pack_escapes.argtypes = [P, LL, LL, U, U, P, P, P, P, P]
+    lib.agd_dense_pack_row_words.restype = LL
+    lib.agd_dense_pack_row_words.argtypes = [LL]
     lib.agd_dense_eval_packed.restype = I
     lib.agd_dense_eval_packed.argtypes = [P, U, U, P, P, P, P, P, P, LL, P, P, P, P, LL, LL,
                                           P, P, P, P, P, LL, I, I, I, I, I, P, P]
@@ -383,29 +385,30 @@ def dense_pack_hist(features: torch.Tensor) -> torch.Tensor:
 
 
 def dense_pack_encode(features: torch.Tensor, lut_lo: int, lut_hi: int):
-    """(packed [n, row bytes] uint8, esc_count [n] int32, per-group escape
-    masks [n, row bytes / 12] uint8) for the given table."""
+    """(packed [n, row bytes] uint8, esc_count [n] int32, escape words
+    [n, row groups / 64] int64: one bit per group) for the given table."""
     lib = load()
     n, d = features.shape
     row_bytes = int(lib.agd_dense_pack_row_bytes(d))
     packed = torch.empty((n, row_bytes), dtype=torch.uint8, device=features.device)
     esc_count = torch.empty(n, dtype=torch.int32, device=features.device)
-    flags = torch.empty((n, row_bytes // 12), dtype=torch.uint8, device=features.device)
+    flags = torch.empty((n, int(lib.agd_dense_pack_row_words(d))), dtype=torch.int64,
+                        device=features.device)
     _check(lib.agd_dense_pack_encode(_ptr(features), n, d, lut_lo, lut_hi,
                                      _ptr(packed), _ptr(esc_count), _ptr(flags),
                                      _stream(features)))
     return packed, esc_count, flags
 
 
-def dense_pack_escapes(features: torch.Tensor, flags: torch.Tensor,
-                       rowptr: torch.Tensor, nnz: int):
+def dense_pack_escapes(features: torch.Tensor, lut_lo: int, lut_hi: int,
+                       flags: torch.Tensor, rowptr: torch.Tensor, nnz: int):
     """Row-sorted escape coordinates (col int32, val f32) for rowptr [n+1],
-    from the escape masks the encode pass wrote."""
+    from the escape words the encode pass wrote under the same table."""
     lib = load()
     n, d = features.shape
     col = torch.empty(nnz, dtype=torch.int32, device=features.device)
     val = torch.empty(nnz, dtype=torch.float32, device=features.device)
-    _check(lib.agd_dense_pack_escapes(_ptr(features), n, d, _ptr(flags),
+    _check(lib.agd_dense_pack_escapes(_ptr(features), n, d, lut_lo, lut_hi, _ptr(flags),
                                       _ptr(rowptr), _ptr(col), _ptr(val),
                                       _stream(features)))
     return col, val

@@ -40,10 +40,11 @@ PACK_MIN_BYTES = 256 << 20
 #: iterations after which the one-time pack has paid for itself. ``auto``
 #: packs before iteration 1 of a solve, normally the first pack of the
 #: process, so the gate is the cold figure: measured on MI355X at
-#: 16384 x 10^6 the first pack of a process takes 79-86 ms and an iteration
-#: saves 2.21 ms, 36-39 iterations, rounded up (profiles/pack_bench.log).
-#: A later pack in the same process takes 20 ms (9 iterations).
-PACK_BREAK_EVEN_ITERS = 40
+#: 16384 x 10^6 the first pack of a process takes 77-84 ms and an iteration
+#: saves 2.43 ms, 32-35 iterations, rounded up
+#: (profiles/pack_stream_tails.log). A later pack in the same process takes
+#: 19 ms (8 iterations).
+PACK_BREAK_EVEN_ITERS = 35
 
 #: device memory that must stay free after the 0.75x copy is allocated
 PACK_HEADROOM_BYTES = 8 << 30
@@ -170,7 +171,8 @@ def encode_with_table(features: torch.Tensor, table: Sequence[int],
             dev = features.device
             rowptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
             torch.cumsum(esc_count, 0, dtype=torch.int32, out=rowptr[1:])
-            col, val = hip.dense_pack_escapes(features, flags, rowptr, n_esc)
+            col, val = hip.dense_pack_escapes(features, lo, hi, flags, rowptr,
+                                              n_esc)
             rows = torch.repeat_interleave(
                 torch.arange(n, dtype=torch.int32, device=dev),
                 esc_count.long(), output_size=n_esc)
