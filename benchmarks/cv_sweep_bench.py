@@ -22,6 +22,10 @@ update k_at_margin_update_tasks). The untracked way is the mixed sweep before
 that kernel existed and what an L1 or elastic-net sweep still runs: the A/B
 of tracking comes from one alternating run.
 
+With --packed every batched (and untracked) row is also timed on a packed
+copy of the same shard (DenseShard.pack(): the packed multi-column MFMA
+kernels), alternating with the raw row inside each round.
+
 Each timed unit is one run() of --warmup + --steps iterations whose last
 --steps are bracketed by device synchronises; the sequential figure is the
 SUM of the R runs' ms/step. The ways alternate, one of each per round, after
@@ -74,7 +78,8 @@ def timed_run(shard, gradient, updater, reg, dim, warmup, steps,
     return (t["t1"] - t["t0"]) * 1e3 / steps
 
 
-def sweep(shard, folds, n_folds, lams, warmup, steps, rounds):
+def sweep(shard, folds, n_folds, lams, warmup, steps, rounds, packed=None,
+          with_sequential=True):
     holdout = [f for _ in lams for f in range(n_folds)]
     task_lams = [lam for lam in lams for _ in range(n_folds)]
     r = len(holdout)
@@ -86,8 +91,8 @@ def sweep(shard, folds, n_folds, lams, warmup, steps, rounds):
     else:
         upd, reg = l2, task_lams[0]
 
-    def batched(track_margins=True):
-        return timed_run(shard, grad, upd, reg, shard.d * r, warmup, steps,
+    def batched(track_margins=True, on=shard):
+        return timed_run(on, grad, upd, reg, shard.d * r, warmup, steps,
                          track_margins)
 
     def sequential():
@@ -95,17 +100,32 @@ def sweep(shard, folds, n_folds, lams, warmup, steps, rounds):
                              warmup, steps) for lam in task_lams)
 
     # one untimed round: code objects, allocator
-    batched(), (batched(False) if mixed else None), sequential()
-    b, u, s = [], [], []
+    batched(), (batched(False) if mixed else None)
+    if with_sequential:
+        sequential()
+    if packed is not None:
+        batched(on=packed), (batched(False, packed) if mixed else None)
+    b, u, s, pb, pu = [], [], [], [], []
     for _ in range(rounds):
         b.append(batched())
+        if packed is not None:  # the packed rows alternate with the raw ones
+            pb.append(batched(on=packed))
         if mixed:
             u.append(batched(False))
-        s.append(sequential())
+            if packed is not None:
+                pu.append(batched(False, packed))
+        s.append(sequential() if with_sequential else float("nan"))
     res = {}
+    if pb:
+        res.update({"packed_batched_ms_per_step": statistics.median(pb),
+                    "packed_batched_min": min(pb), "packed_batched_rounds": pb})
+    if pu:
+        res.update({"packed_untracked_ms_per_step": statistics.median(pu),
+                    "packed_untracked_min": min(pu),
+                    "packed_untracked_rounds": pu})
     if mixed:
-        res = {"untracked_ms_per_step": statistics.median(u),
-               "untracked_min": min(u), "untracked_rounds": u}
+        res.update({"untracked_ms_per_step": statistics.median(u),
+                    "untracked_min": min(u), "untracked_rounds": u})
     return {**res, "tasks": r,
             "batched_ms_per_step": statistics.median(b),
             "batched_min": min(b),
@@ -126,6 +146,13 @@ def report(title, res):
         print(f"  untracked   median {u:9.3f} ms/step  min {res['untracked_min']:9.3f}"
               f"   (the same run, track_margins=False: {u / b:.2f}x the tracked)",
               flush=True)
+    for way, raw in (("batched", b), ("untracked", res.get("untracked_ms_per_step"))):
+        key = f"packed_{way}_ms_per_step"
+        if key in res:
+            rounds = res[f"packed_{way}_rounds"]
+            print(f"  packed {way:9s} median {res[key]:9.3f} ms/step  min "
+                  f"{min(rounds):9.3f} max {max(rounds):9.3f}   (the packed MFMA "
+                  f"kernels: {res[key] / raw:.3f}x the raw {way} row)", flush=True)
     print(f"  sequential  median {s:9.3f} ms/step  min {res['sequential_min']:9.3f}"
           f"   (sum of {res['tasks']} runs, each on the WHOLE shard)", flush=True)
     print(f"  sequential x 2/3   {s23:9.3f} ms/step"
@@ -144,6 +171,12 @@ def main():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--rounds", type=int, default=5)
+    p.add_argument("--packed", action="store_true",
+                   help="add rows for the same sweeps on a packed copy of the "
+                        "shard (the packed multi-column MFMA kernels), "
+                        "alternating with the raw rows")
+    p.add_argument("--skip-sequential", action="store_true",
+                   help="leave the R sequential runs out (their figures are nan)")
     args = p.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("cv_sweep_bench needs a GPU (no CPU fallback for timings)")
@@ -160,15 +193,25 @@ def main():
     out = {"rows": args.rows, "d": args.d, "folds": args.folds,
            "lambdas": args.lambdas, "warmup": args.warmup,
            "steps": args.steps, "rounds": args.rounds}
+    packed = None
+    if args.packed:
+        from sparkagd_amd.data import DenseShard
+
+        packed = DenseShard(shard.features, shard.labels)
+        if not packed.pack():
+            raise SystemExit(f"pack refused: {packed.pack_refused}")
+        print(f"packed copy: {packed._packed.nbytes / 1e9:.2f} GB, "
+              f"{packed._packed.nnz} escapes", flush=True)
+    extra = dict(packed=packed, with_sequential=not args.skip_sequential)
     mid = args.lambdas[len(args.lambdas) // 2]
     out["equal_lambda_tracked"] = sweep(
         shard, folds, args.folds, [mid] * len(args.lambdas), args.warmup,
-        args.steps, args.rounds)
+        args.steps, args.rounds, **extra)
     report(f"equal lambda ({mid:g}): plain updater, margins tracked",
            out["equal_lambda_tracked"])
     out["mixed_lambda"] = sweep(
         shard, folds, args.folds, args.lambdas, args.warmup, args.steps,
-        args.rounds)
+        args.rounds, **extra)
     report("mixed lambdas: PerTaskUpdater, margins tracked per column",
            out["mixed_lambda"])
     out["shard_packed_by_policy"] = bool(shard.is_packed)

@@ -31,6 +31,9 @@ def main():
     p.add_argument("--folds", type=int, default=3)
     p.add_argument("--lambdas", type=float, nargs="+",
                    default=[1e-4, 1e-3, 1e-2, 1e-1])
+    p.add_argument("--pack", action="store_true",
+                   help="pack a bf16 GPU shard first: the sweep then streams "
+                        "the 12-bit copy through the packed MFMA kernels")
     args = p.parse_args()
 
     if torch.cuda.is_available():
@@ -44,7 +47,7 @@ def main():
     res = cross_validate(
         shard, args.lambdas, n_folds=args.folds, gradient=LogisticGradient(),
         num_iterations=args.iters,
-        config=AGDConfig(loss_history_mode="backtrack"))
+        config=AGDConfig(loss_history_mode="backtrack"), pack=args.pack)
 
     print(f"{len(args.lambdas)} lambdas x {args.folds} folds = "
           f"{len(args.lambdas) * args.folds} models in one run "

@@ -32,7 +32,9 @@
 //  * No Triton, no CUDA-compat headers, no torch headers: plain HIP + a C ABI
 //    taking raw device pointers and a hipStream_t, loaded via ctypes.
 //
-// Build: hipcc --offload-arch=gfx950 -O3 -shared -fPIC agd_kernels.hip -o libagd_hip.so
+// Build: hipcc --offload-arch=gfx950 -O3 -fPIC -c agd_kernels.hip, then linked
+// with agd_multi_packed.o (the packed multi-column MFMA kernels) into
+// libagd_hip.so; see __graft_entry__.build().
 
 #include <hip/hip_runtime.h>
 #include <hipblaslt/hipblaslt.h>
@@ -2787,6 +2789,33 @@ extern "C" long long agd_multi_rowblocks(long long n, long long d, int kc) {
   if (n_rb > n) n_rb = n;
   while (n_rb > 1 && n_rb * d * kc * 4 > (1LL << 30)) n_rb /= 2;
   return n_rb;
+}
+
+// Host helpers for agd_multi_packed.hip (the packed multi-column MFMA
+// kernels, a translation unit of its own): the library's one error string
+// and the two fixed-order reducers.
+extern "C" void agd_set_last_error(const char* msg) {
+  snprintf(g_err, sizeof(g_err), "%s", msg);
+}
+
+// out[i] = sum over rb (ascending) of part[rb * len + i].
+extern "C" int agd_grad_reduce_f32(const void* part, long long n_rb,
+                                   long long len, void* out, void* stream) {
+  hipLaunchKernelGGL((k_grad_reduce<float>), dim3(grid_for(len, BLOCK)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, (const float*)part,
+                     (ll)n_rb, (ll)len, (float*)out);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// part[i] += part[s * len + i] for s = 1 .. n_slabs-1 (ascending), in place.
+extern "C" int agd_slab_reduce_f32(void* part, long long len, int n_slabs,
+                                   void* stream) {
+  hipLaunchKernelGGL((k_slab_reduce<float>), dim3(grid_for(len, BLOCK)),
+                     dim3(BLOCK), 0, (hipStream_t)stream, (float*)part, (ll)len,
+                     n_slabs);
+  HIP_CHECK(hipGetLastError());
+  return 0;
 }
 
 template <typename TA, int W>

@@ -74,6 +74,7 @@ def cross_validate(
     config: Optional[AGDConfig] = None,
     refit: bool = True,
     fold_id: Optional[torch.Tensor] = None,
+    pack: bool = False,
 ) -> CVResult:
     """k-fold cross-validation of ``lambdas`` for a binary GLM: all
     ``len(lambdas) * n_folds`` models train in one ``run()`` over the shard,
@@ -100,6 +101,12 @@ def cross_validate(
     and a column whose ``step * lambda`` passes 1 does not damp it: with
     lambdas spread over decades under one shared step, a tracked run was
     seen to pick another ``best_lambda`` than the f64 run.
+
+    ``pack=True`` calls ``data.pack()`` first (a dense shard on the GPU): a
+    packed bf16 shard with at most 128 padded tasks then streams its 12-bit
+    copy through the packed MFMA kernels, which carry the f32 weights as a
+    bf16 pair. A refused pack leaves the raw route and the reason in
+    ``data.pack_refused``. The tracking defaults above do not change.
     """
     from .optimizer import run
 
@@ -120,6 +127,8 @@ def cross_validate(
             f"{type(data).__name__}")
     gradient = gradient or LogisticGradient()
     updater = updater or SquaredL2Updater()
+    if pack and data.kind == "dense" and data.features.is_cuda:
+        data.pack()
     n_l, n_f = len(lams), int(n_folds)
     if fold_id is None:
         fold_id = assign_folds(data.n, n_f, seed, comm.rank)

@@ -147,6 +147,12 @@ class MultinomialLogisticGradient(Gradient):
         if getattr(shard, "kind", None) == "csr":
             return mc.eval_multi_csr(shard, w, self.num_classes, mask,
                                      need_grad, shard.sample_weight)
+        pk = mc.packed_copy_for(shard, self.num_classes)
+        if pk is not None:
+            z = ops.margins_multi_packed(pk, w, self.num_classes)
+            return mc.eval_multi_packed_from_margins(
+                pk, z, shard.labels, self.num_classes, mask, need_grad,
+                shard.sample_weight)
         return mc.eval_multi(shard.features, shard.labels, w, self.num_classes,
                              mask, need_grad, shard.sample_weight)
 
@@ -156,6 +162,9 @@ class MultinomialLogisticGradient(Gradient):
         self._check_shard(shard)
         if getattr(shard, "kind", None) == "csr":
             return mc.csr_margins_multi(shard, v, self.num_classes)
+        pk = mc.packed_copy_for(shard, self.num_classes)
+        if pk is not None:
+            return ops.margins_multi_packed(pk, v, self.num_classes)
         return mc.margins_multi(shard.features, v, self.num_classes)
 
     def eval_from_margins(self, shard, margins, mask=None, need_grad=True):
@@ -167,6 +176,11 @@ class MultinomialLogisticGradient(Gradient):
                                                   self.num_classes, mask,
                                                   need_grad,
                                                   shard.sample_weight)
+        pk = mc.packed_copy_for(shard, self.num_classes)
+        if pk is not None:
+            return mc.eval_multi_packed_from_margins(
+                pk, margins, shard.labels, self.num_classes, mask, need_grad,
+                shard.sample_weight)
         return mc.eval_multi_from_margins(shard.features, margins, shard.labels,
                                           self.num_classes, mask, need_grad,
                                           shard.sample_weight)

@@ -20,6 +20,7 @@ from typing import Optional, Sequence
 
 import torch
 
+from .. import ops
 from .gradient import Gradient
 from .updater import (ElasticNetUpdater, FreeTailUpdater, SimpleUpdater,
                       SquaredL2Updater, Updater)
@@ -171,6 +172,10 @@ class MultiTaskGradient(Gradient):
         self._check_shard(shard)
         if shard.kind == "csr":
             return mc.csr_margins_multi(shard, v, self.num_tasks)
+        pk = mc.packed_copy_for(shard, self.num_tasks)
+        if pk is not None:
+            # W goes in as bf16 hi + lo: one pass serves training and scoring
+            return ops.margins_multi_packed(pk, v, self.num_tasks)
         if scoring:
             return mt.dense_margins_scoring(shard.features, v, self.num_tasks)
         return mc.margins_multi(shard.features, v, self.num_tasks)
@@ -202,6 +207,7 @@ class MultiTaskGradient(Gradient):
         return m, lc
 
     def eval_from_margins(self, shard, margins, mask=None, need_grad=True):
+        from ..ops import multiclass as mc
         from ..ops import multitask as mt
 
         if not need_grad:
@@ -211,6 +217,10 @@ class MultiTaskGradient(Gradient):
         m, lc = self.multiplier_loss(shard, margins, mask)
         if shard.kind == "csr":
             return mt.csr_grad_tasks(shard, m, self.num_tasks), lc
+        pk = mc.packed_copy_for(shard, self.num_tasks)
+        if pk is not None:
+            return ops.grad_multi_packed(pk, m, self.num_tasks,
+                                         split_m=True), lc
         return mt.dense_grad_tasks(shard.features, m, self.num_tasks), lc
 
     def eval(self, shard, w, mask=None, need_grad=True):

@@ -415,17 +415,26 @@ class SoftmaxRegressionWithAGD:
         comm: Optional[Communicator] = None,
         config: Optional[AGDConfig] = None,
         feature_scaling: Union[bool, str] = False,
+        pack: bool = False,
     ) -> MultinomialModel:
         """``feature_scaling``: ``False`` | ``True`` | ``"inplace"``, as in
         the binary GLM trainers (column standardisation before optimising;
         ``True`` holds a scaled copy of the features during training; the
         regulariser acts on the scaled-space weights; returned weights and
-        ``initial_weights`` are in the original feature space)."""
+        ``initial_weights`` are in the original feature space).
+
+        ``pack=True`` packs a dense GPU shard first (``DenseShard.pack()``):
+        a packed bf16 shard with ``padded_k(num_classes) <= 128`` trains on
+        the packed MFMA kernels; a refusal leaves the raw route and the
+        reason in the shard's ``pack_refused``."""
         from ..stats import scaled_training_data
         from .gradient import MultinomialLogisticGradient
 
         data, scaler, initial_weights = scaled_training_data(
             data, feature_scaling, comm, initial_weights, num_classes)
+        if (pack and getattr(data, "kind", None) == "dense"
+                and data.features.is_cuda):
+            data.pack()
 
         cfg = config or AGDConfig()
         cfg.num_iterations = num_iterations

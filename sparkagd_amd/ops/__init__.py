@@ -133,6 +133,45 @@ def dense_grad_from_mult_packed(pk, mult: torch.Tensor) -> torch.Tensor:
     return _get_hip().dense_grad_from_mult_packed(pk, mult)
 
 
+# Multi-column passes (softmax, multi-task sweeps) over a packed copy: the
+# hand-written MFMA kernels, flat padded conventions of ops.multiclass.
+MULTI_PACKED_MAX_KC = 128
+
+
+def multi_packed_serves(pk, k: int) -> bool:
+    """True when the packed multi-column kernels take this copy and width."""
+    from .multiclass import padded_k
+
+    return pk is not None and padded_k(k) <= MULTI_PACKED_MAX_KC
+
+
+def margins_multi_packed(pk, wflat: torch.Tensor, k: int) -> torch.Tensor:
+    """Flat padded margins [n*KC] = A·W (``multiclass.margins_multi``'s
+    layout, pad columns exact zeros) with the exact f32 weights carried as
+    bf16 hi + lo operands."""
+    from .multiclass import padded_k
+
+    return _get_hip().margins_multi_packed(pk, wflat, k, padded_k(k))
+
+
+def grad_multi_packed(pk, m_padded_flat: torch.Tensor, k: int,
+                      split_m: bool = False) -> torch.Tensor:
+    """grad flat [d*k] = Aᵀ·M from the padded multiplier [n*KC]
+    (``multiclass.grad_from_mult_multi``'s conventions; M rounded to bf16
+    once, as on the GEMM route). ``split_m=True`` carries M as
+    ``bf16(M) + bf16(M − bf16(M))``, a second MFMA per fragment: the solver
+    routes use it, because the rounding of M is a gradient error that does
+    not shrink near the optimum (it was measured to swallow the restart test
+    of a mixed-λ sweep, after which the largest λ's columns diverged)."""
+    from .multiclass import padded_k
+
+    kc = padded_k(k)
+    gradp = _get_hip().grad_multi_packed(pk, m_padded_flat, kc, split_m)
+    if kc != k:
+        return gradp.reshape(pk.d, kc)[:, :k].reshape(-1).contiguous()
+    return gradp
+
+
 def dense_pack_decode(pk, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [n, d] from a packed copy, bit for bit: the HIP decoder on the
     GPU, ``packing.decode_torch`` elsewhere."""

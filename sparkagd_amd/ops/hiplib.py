@@ -74,6 +74,18 @@ def load() -> ctypes.CDLL:
     lib.agd_dense_pack_row_bytes.argtypes = [LL]
     lib.agd_dense_pack_decode.restype = I
     lib.agd_dense_pack_decode.argtypes = [P, U, U, P, P, P, LL, LL, LL, P, P]
+    lib.agd_multi_packed_slabs.restype = I
+    lib.agd_multi_packed_slabs.argtypes = [LL, LL]
+    lib.agd_multi_packed_wplane_elems.restype = LL
+    lib.agd_multi_packed_wplane_elems.argtypes = [LL, I]
+    lib.agd_multi_packed_mplane_elems.restype = LL
+    lib.agd_multi_packed_mplane_elems.argtypes = [LL, I]
+    lib.agd_margins_multi_packed.restype = I
+    lib.agd_margins_multi_packed.argtypes = [P, U, U, P, P, P, LL, P, LL, LL, I, I,
+                                             P, P, P, I, P]
+    lib.agd_grad_multi_packed.restype = I
+    lib.agd_grad_multi_packed.argtypes = [P, U, U, P, P, P, LL, P, LL, LL, I, P, P,
+                                          P, LL, P, P]
     lib.agd_csr_eval.restype = I
     lib.agd_csr_eval.argtypes = [P, P, P, P, P, P, P, LL, LL, LL, P, P, P, P, I, P, P, P, I, I, P, P]
     lib.agd_axpby.restype = I
@@ -509,6 +521,56 @@ def dense_eval_from_margins_packed(pk, margins, labels, loss_type, mask=None,
 def dense_grad_from_mult_packed(pk, mult: torch.Tensor) -> torch.Tensor:
     assert mult.dtype == torch.float32 and mult.numel() == pk.n
     grad, _, _ = _packed_call(pk, 3, mult=mult.contiguous(), need_grad=True)
+    return grad
+
+
+def margins_multi_packed(pk, wflat: torch.Tensor, k: int, kc: int) -> torch.Tensor:
+    """Flat padded margins [n*kc] = A·W from a PackedDense copy: the MFMA
+    kernel over the packed rows with W as bf16 hi + lo planes, the slab
+    partials reduced in fixed order, then the escapes with the f32 W."""
+    lib = load()
+    n, d = pk.n, pk.d
+    dev = pk.packed.device
+    if wflat.dtype != torch.float32 or wflat.numel() != d * k:
+        raise TypeError(f"weights must be the f32 [d*k] flat, got {wflat.dtype} "
+                        f"[{wflat.numel()}] for d={d} k={k}")
+    n_slabs = int(lib.agd_multi_packed_slabs(n, d))
+    plane = int(lib.agd_multi_packed_wplane_elems(d, kc))
+    planes = torch.empty((2, plane), dtype=torch.bfloat16, device=dev)
+    z = torch.empty(n_slabs * n * kc, dtype=torch.float32, device=dev)
+    e = pk.esc
+    _check(lib.agd_margins_multi_packed(
+        _ptr(pk.packed), pk.lut_lo, pk.lut_hi, _ptr(e["rowptr"]), _ptr(e["col"]),
+        _ptr(e["val"]), pk.nnz, _ptr(wflat.contiguous()), n, d, k, kc,
+        _ptr(planes[0]), _ptr(planes[1]), _ptr(z), n_slabs, _stream(pk.packed)))
+    return z.narrow(0, 0, n * kc)
+
+
+def grad_multi_packed(pk, m_padded_flat: torch.Tensor, kc: int,
+                      split_m: bool = False) -> torch.Tensor:
+    """Padded gradient flat [d*kc] = Aᵀ·bf16(M) from a PackedDense copy and
+    the padded f32 multiplier [n*kc]; row-block partials reduced in fixed
+    order (bitwise reproducible), then the escapes. ``split_m`` carries M as
+    a bf16 hi + lo pair instead: Aᵀ·M of the f32 multiplier."""
+    lib = load()
+    n, d = pk.n, pk.d
+    dev = pk.packed.device
+    if m_padded_flat.dtype != torch.float32 or m_padded_flat.numel() != n * kc:
+        raise TypeError(f"multiplier must be the f32 [n*kc] flat, got "
+                        f"{m_padded_flat.dtype} [{m_padded_flat.numel()}]")
+    n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
+    mt = torch.empty((2 if split_m else 1,
+                      int(lib.agd_multi_packed_mplane_elems(n, kc))),
+                     dtype=torch.bfloat16, device=dev)
+    grad = torch.empty(d * kc, dtype=torch.float32, device=dev)
+    part = (torch.empty(n_rb * d * kc, dtype=torch.float32, device=dev)
+            if n_rb > 1 else grad)
+    e = pk.esc
+    _check(lib.agd_grad_multi_packed(
+        _ptr(pk.packed), pk.lut_lo, pk.lut_hi, _ptr(e["colptr"]), _ptr(e["row"]),
+        _ptr(e["cval"]), pk.nnz, _ptr(m_padded_flat.contiguous()), n, d, kc,
+        _ptr(mt[0]), _ptr(mt[1]) if split_m else None, _ptr(part), n_rb,
+        _ptr(grad), _stream(pk.packed)))
     return grad
 
 

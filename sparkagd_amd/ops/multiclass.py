@@ -253,6 +253,32 @@ def eval_multi_from_margins(features, margins_padded_flat, labels, k,
     return grad, lc
 
 
+def packed_copy_for(shard, k: int):
+    """The shard's packed copy when the packed multi-column kernels serve it
+    (a dense shard that already is packed, on the GPU, padded_k(k) <= 128),
+    else None: the caller keeps the raw route."""
+    from . import multi_packed_serves
+
+    if getattr(shard, "kind", None) != "dense":
+        return None
+    pk = shard._packed_gpu()
+    return pk if multi_packed_serves(pk, k) else None
+
+
+def eval_multi_packed_from_margins(pk, margins_padded_flat, labels, k,
+                                   mask=None, need_grad=True,
+                                   sample_weight=None):
+    """``eval_multi_from_margins`` on a packed copy: the multiplier kernel,
+    then Aᵀ·M by the packed MFMA gradient kernel."""
+    from . import grad_multi_packed
+
+    M, loss_count = multiplier_loss_multi(labels, margins_padded_flat, k, mask,
+                                          sample_weight)
+    if not need_grad:
+        return None, loss_count
+    return grad_multi_packed(pk, M, k, split_m=True), loss_count
+
+
 def eval_multi(features, labels, wflat, k, mask=None, need_grad=True,
                sample_weight=None):
     zf = margins_multi(features, wflat, k)
