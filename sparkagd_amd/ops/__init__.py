@@ -172,6 +172,47 @@ def grad_multi_packed(pk, m_padded_flat: torch.Tensor, k: int,
     return gradp
 
 
+# Multi-column passes over a raw fp8 (e4m3fn) dense shard: the MFMA kernels
+# k_margins_multi_f8 / k_grad_multi_f8, any class width.
+def multi_fp8_serves(features: torch.Tensor, k: int) -> bool:
+    """True when the fp8 multi-column MFMA kernels take this feature block:
+    e4m3fn on the GPU, contiguous rows of ``d % 16 == 0`` bytes from a
+    16-byte-aligned base."""
+    return (_use_hip(features) and features.dtype == torch.float8_e4m3fn
+            and features.dim() == 2 and features.is_contiguous()
+            and features.shape[1] % 16 == 0 and features.data_ptr() % 16 == 0
+            and k >= 1)
+
+
+def margins_multi_fp8(features: torch.Tensor, wflat: torch.Tensor,
+                      k: int) -> torch.Tensor:
+    """Flat padded margins [n*KC] = A·W (``multiclass.margins_multi``'s
+    layout, pad columns exact zeros) on an fp8 shard, the exact f32 weights
+    carried as bf16 hi + lo operands."""
+    from .multiclass import padded_k
+
+    if not multi_fp8_serves(features, k):
+        raise ValueError("margins_multi_fp8 needs a contiguous float8_e4m3fn "
+                         "GPU block with d % 16 == 0 and a 16-byte-aligned base")
+    return _get_hip().margins_multi_fp8(features, wflat, k, padded_k(k))
+
+
+def grad_multi_fp8(features: torch.Tensor, m_padded_flat: torch.Tensor, k: int,
+                   split_m: bool = False) -> torch.Tensor:
+    """grad flat [d*k] = Aᵀ·M on an fp8 shard from the padded multiplier
+    [n*KC]; ``split_m`` as in ``grad_multi_packed``."""
+    from .multiclass import padded_k
+
+    if not multi_fp8_serves(features, k):
+        raise ValueError("grad_multi_fp8 needs a contiguous float8_e4m3fn "
+                         "GPU block with d % 16 == 0 and a 16-byte-aligned base")
+    kc = padded_k(k)
+    gradp = _get_hip().grad_multi_fp8(features, m_padded_flat, kc, split_m)
+    if kc != k:
+        return gradp.reshape(features.shape[1], kc)[:, :k].reshape(-1).contiguous()
+    return gradp
+
+
 def dense_pack_decode(pk, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """bf16 [n, d] from a packed copy, bit for bit: the HIP decoder on the
     GPU, ``packing.decode_torch`` elsewhere."""

@@ -86,6 +86,14 @@ def load() -> ctypes.CDLL:
     lib.agd_grad_multi_packed.restype = I
     lib.agd_grad_multi_packed.argtypes = [P, U, U, P, P, P, LL, P, LL, LL, I, P, P,
                                           P, LL, P, P]
+    lib.agd_multi_f8_slabs.restype = I
+    lib.agd_multi_f8_slabs.argtypes = [LL, LL]
+    lib.agd_multi_f8_wplane_elems.restype = LL
+    lib.agd_multi_f8_wplane_elems.argtypes = [LL, I]
+    lib.agd_margins_multi_f8.restype = I
+    lib.agd_margins_multi_f8.argtypes = [P, P, LL, LL, I, I, P, P, P, I, P]
+    lib.agd_grad_multi_f8.restype = I
+    lib.agd_grad_multi_f8.argtypes = [P, P, LL, LL, I, P, P, P, LL, P, P]
     lib.agd_csr_eval.restype = I
     lib.agd_csr_eval.argtypes = [P, P, P, P, P, P, P, LL, LL, LL, P, P, P, P, I, P, P, P, I, I, P, P]
     lib.agd_axpby.restype = I
@@ -574,6 +582,53 @@ def grad_multi_packed(pk, m_padded_flat: torch.Tensor, kc: int,
     return grad
 
 
+def margins_multi_fp8(features: torch.Tensor, wflat: torch.Tensor, k: int,
+                      kc: int) -> torch.Tensor:
+    """Flat padded margins [n*kc] = A·W from an fp8 e4m3fn shard: the MFMA
+    kernel over the raw byte rows with W as bf16 hi + lo planes, the slab
+    partials reduced in fixed order."""
+    lib = load()
+    n, d = features.shape
+    dev = features.device
+    if wflat.dtype != torch.float32 or wflat.numel() != d * k:
+        raise TypeError(f"weights must be the f32 [d*k] flat, got {wflat.dtype} "
+                        f"[{wflat.numel()}] for d={d} k={k}")
+    n_slabs = int(lib.agd_multi_f8_slabs(n, d))
+    plane = int(lib.agd_multi_f8_wplane_elems(d, kc))
+    planes = torch.empty((2, plane), dtype=torch.bfloat16, device=dev)
+    z = torch.empty(n_slabs * n * kc, dtype=torch.float32, device=dev)
+    _check(lib.agd_margins_multi_f8(
+        _ptr(features), _ptr(wflat.contiguous()), n, d, k, kc, _ptr(planes[0]),
+        _ptr(planes[1]), _ptr(z), n_slabs, _stream(features)))
+    return z.narrow(0, 0, n * kc)
+
+
+def grad_multi_fp8(features: torch.Tensor, m_padded_flat: torch.Tensor,
+                   kc: int, split_m: bool = False) -> torch.Tensor:
+    """Padded gradient flat [d*kc] = Aᵀ·bf16(M) from an fp8 e4m3fn shard and
+    the padded f32 multiplier [n*kc]; row-block partials reduced in fixed
+    order (bitwise reproducible). ``split_m`` carries M as a bf16 hi + lo
+    pair instead: Aᵀ·M of the f32 multiplier."""
+    lib = load()
+    n, d = features.shape
+    dev = features.device
+    if m_padded_flat.dtype != torch.float32 or m_padded_flat.numel() != n * kc:
+        raise TypeError(f"multiplier must be the f32 [n*kc] flat, got "
+                        f"{m_padded_flat.dtype} [{m_padded_flat.numel()}]")
+    n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
+    mt = torch.empty((2 if split_m else 1,
+                      int(lib.agd_multi_packed_mplane_elems(n, kc))),
+                     dtype=torch.bfloat16, device=dev)
+    grad = torch.empty(d * kc, dtype=torch.float32, device=dev)
+    part = (torch.empty(n_rb * d * kc, dtype=torch.float32, device=dev)
+            if n_rb > 1 else grad)
+    _check(lib.agd_grad_multi_f8(
+        _ptr(features), _ptr(m_padded_flat.contiguous()), n, d, kc, _ptr(mt[0]),
+        _ptr(mt[1]) if split_m else None, _ptr(part), n_rb, _ptr(grad),
+        _stream(features)))
+    return grad
+
+
 def _csc_grad_skew(csc, csc_heavy, mult: torch.Tensor, d: int) -> torch.Tensor:
     """Deterministic skew-robust CSC gradient: light thread-per-column pass
     for columns <= heavy_T nnz + wave-per-task partials for split heavy
@@ -829,6 +884,8 @@ def dense_eval_multi_from_margins(
     need_grad: bool = True,
     sample_weight: Optional[torch.Tensor] = None,
 ) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
+    from . import multi_fp8_serves
+
     lib = load()
     n, d = features.shape
     a_dtype = _DTYPE_CODE[features.dtype]
@@ -845,6 +902,9 @@ def dense_eval_multi_from_margins(
         # (standard mixed precision; A is bf16, accumulation f32);
         # SPARKAGD_MULTI_GRAD=valu selects the exact-f32-multiplier kernel.
         gradp = gemm_bf16f32_tn(features, M.reshape(n, kc)).reshape(-1)
+    elif algo == "mfma" and multi_fp8_serves(features, k):
+        # opt-in below 33 columns: the fp8 MFMA kernel, M as bf16 hi + lo
+        gradp = grad_multi_fp8(features, M, kc, split_m=True)
     else:
         n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
         gradp = torch.empty(d * kc, dtype=torch.float32, device=dev)

@@ -40,7 +40,7 @@ def padded_k(k: int) -> int:
     """Class-dim padding: snapped to the VALU kernel template sizes
     (4/8/16/32) for small K; plain ceil-4 padding above 32, where the GPU
     path runs GEMM-shaped (hipBLASLt margins/grad + torch multiplier stage —
-    bf16 or f32 shards)."""
+    bf16 or f32 shards) or, on fp8 shards, the fp8 MFMA kernels."""
     for kc in (4, 8, 16, 32):
         if k <= kc:
             return kc
@@ -186,7 +186,7 @@ def margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int) -> torch.
 
     kc = padded_k(k)
     if _use_hip(features):
-        from . import hiplib
+        from . import hiplib, margins_multi_fp8, multi_fp8_serves
 
         algo = os.environ.get("SPARKAGD_MULTI_MARGINS", "auto")
         if kc > 32:
@@ -197,10 +197,15 @@ def margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int) -> torch.
                 # rocBLAS via torch.mm is the idiomatic f32 library GEMM
                 z = features @ wflat.reshape(features.shape[1], k).to(torch.float32)
                 return _pad_classes(z, kc).reshape(-1)
+            if multi_fp8_serves(features, k):
+                return margins_multi_fp8(features, wflat, k)
             raise NotImplementedError(
-                f"K={k} > 32 margins need a bf16 (hipBLASLt) or f32 (rocBLAS) shard")
+                f"K={k} > 32 margins need a bf16 (hipBLASLt) or f32 (rocBLAS) "
+                "shard, or an fp8 shard with d % 16 == 0 (MFMA kernel)")
         if features.dtype == torch.bfloat16 and algo in ("auto", "gemm"):
             return _gemm_margins_multi(features, wflat, k, kc)
+        if algo == "mfma" and multi_fp8_serves(features, k):
+            return margins_multi_fp8(features, wflat, k)
         return hiplib.dense_margins_multi(features, wflat, k, kc)
     z = ref_margins_multi(features, wflat, k).reshape(features.shape[0], k)
     return _pad_classes(z, kc).reshape(-1)
@@ -229,8 +234,13 @@ def _eval_large_k_from_margins(features, margins_padded_flat, labels, k, kc,
     if features.dtype == torch.float32:
         m = M.reshape(n, kc)[:, :k]
         return (features.T @ m).reshape(-1), loss_count
+    from . import grad_multi_fp8, multi_fp8_serves
+
+    if multi_fp8_serves(features, k):
+        return grad_multi_fp8(features, M, k, split_m=True), loss_count
     raise NotImplementedError(
-        f"K={k} > 32 gradient needs a bf16 (hipBLASLt) or f32 (rocBLAS) shard")
+        f"K={k} > 32 gradient needs a bf16 (hipBLASLt) or f32 (rocBLAS) shard, "
+        "or an fp8 shard with d % 16 == 0 (MFMA kernel)")
 
 
 def eval_multi_from_margins(features, margins_padded_flat, labels, k,
@@ -396,16 +406,19 @@ def grad_from_mult_multi(features, m_padded_flat, k):
     if _use_hip(features):
         import os
 
-        from . import hiplib
+        from . import grad_multi_fp8, hiplib, multi_fp8_serves
 
-        if (features.dtype == torch.bfloat16
-                and os.environ.get("SPARKAGD_MULTI_GRAD", "auto") != "valu"):
+        algo = os.environ.get("SPARKAGD_MULTI_GRAD", "auto")
+        if features.dtype == torch.bfloat16 and algo != "valu":
             gradp = hiplib.gemm_bf16f32_tn(
                 features, m_padded_flat.reshape(n, kc)).reshape(-1)
+        elif (kc > 32 or algo == "mfma") and multi_fp8_serves(features, k):
+            return grad_multi_fp8(features, m_padded_flat, k, split_m=True)
         else:
             if kc > 32:
                 raise NotImplementedError(
-                    "K > 32 VALU grad unsupported — bf16 shards use the GEMM")
+                    "K > 32 VALU grad unsupported — bf16 shards use the GEMM, "
+                    "fp8 shards with d % 16 == 0 the MFMA kernel")
             lib = hiplib.load()
             n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
             gradp = torch.empty(d * kc, dtype=torch.float32,

@@ -216,7 +216,8 @@ def dense_margins_scoring(features: torch.Tensor, wflat: torch.Tensor,
     Here W goes in as bf16(W) + bf16(W - bf16(W)), two accumulating
     hipBLASLt GEMMs (2^-17 per weight) at about twice the one-GEMM cost — the
     exact-f32 VALU kernel would cost ~12 A-streams. Every other shard dtype
-    already multiplies the exact weights."""
+    already multiplies the exact weights (an fp8 shard with more than 32
+    columns through ``margins_multi_fp8``, W as bf16 hi + lo)."""
     from .multiclass import margins_multi
 
     if not (_use_hip(features) and features.dtype == torch.bfloat16):
@@ -239,7 +240,9 @@ def dense_grad_tasks(features: torch.Tensor, m_padded_flat: torch.Tensor,
                      k: int) -> torch.Tensor:
     """grad flat [d*k] = Aᵀ·M on a dense shard: ``grad_from_mult_multi``,
     plus the rocBLAS route the multinomial path takes for an f32 shard with
-    more than 32 columns (no VALU kernel above the KC=32 template)."""
+    more than 32 columns (no VALU kernel above the KC=32 template). An fp8
+    shard with more than 32 columns runs the MFMA kernel ``k_grad_multi_f8``
+    (inside ``grad_from_mult_multi``; M as a bf16 hi + lo pair)."""
     from .multiclass import grad_from_mult_multi
 
     kc = padded_k(k)
