@@ -19,6 +19,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import ops
+from ..ops import multiclass as mc
 
 
 class Gradient:
@@ -141,55 +142,24 @@ class MultinomialLogisticGradient(Gradient):
                 "is not supported")
 
     def eval(self, shard, w, mask=None, need_grad=True):
-        from ..ops import multiclass as mc
-
-        self._check_shard(shard)
-        if getattr(shard, "kind", None) == "csr":
-            return mc.eval_multi_csr(shard, w, self.num_classes, mask,
-                                     need_grad, shard.sample_weight)
-        pk = mc.packed_copy_for(shard, self.num_classes)
-        if pk is not None:
-            z = ops.margins_multi_packed(pk, w, self.num_classes)
-            return mc.eval_multi_packed_from_margins(
-                pk, z, shard.labels, self.num_classes, mask, need_grad,
-                shard.sample_weight)
-        return mc.eval_multi(shard.features, shard.labels, w, self.num_classes,
-                             mask, need_grad, shard.sample_weight)
+        return self.eval_from_margins(shard, self.margins(shard, w), mask,
+                                      need_grad)
 
     def margins(self, shard, v):
-        from ..ops import multiclass as mc
-
         self._check_shard(shard)
-        if getattr(shard, "kind", None) == "csr":
-            return mc.csr_margins_multi(shard, v, self.num_classes)
-        pk = mc.packed_copy_for(shard, self.num_classes)
-        if pk is not None:
-            return ops.margins_multi_packed(pk, v, self.num_classes)
-        return mc.margins_multi(shard.features, v, self.num_classes)
+        return mc.multi_margins(shard, v, self.num_classes)
 
     def eval_from_margins(self, shard, margins, mask=None, need_grad=True):
-        from ..ops import multiclass as mc
-
         self._check_shard(shard)
-        if getattr(shard, "kind", None) == "csr":
-            return mc.eval_multi_csr_from_margins(shard, margins,
-                                                  self.num_classes, mask,
-                                                  need_grad,
-                                                  shard.sample_weight)
-        pk = mc.packed_copy_for(shard, self.num_classes)
-        if pk is not None:
-            return mc.eval_multi_packed_from_margins(
-                pk, margins, shard.labels, self.num_classes, mask, need_grad,
-                shard.sample_weight)
-        return mc.eval_multi_from_margins(shard.features, margins, shard.labels,
-                                          self.num_classes, mask, need_grad,
-                                          shard.sample_weight)
+        m, loss_count = self.multiplier_loss(shard, margins, mask)
+        if not need_grad:
+            return None, loss_count
+        return mc.multi_grad(shard, m, self.num_classes), loss_count
 
     def multiplier_loss(self, shard, margins, mask=None):
         """(padded multiplier flat [n*KC], loss_count) from padded margins —
-        the Gram solver's n-space evaluation."""
-        from ..ops import multiclass as mc
-
+        the n-space stage (zero data passes); also the Gram solver's
+        evaluation."""
         return mc.multiplier_loss_multi(shard.labels, margins,
                                         self.num_classes, mask,
                                         getattr(shard, "sample_weight", None))

@@ -20,7 +20,7 @@ from typing import Optional, Sequence
 
 import torch
 
-from .. import ops
+from ..ops import multiclass as mc, multitask as mt
 from .gradient import Gradient
 from .updater import (ElasticNetUpdater, FreeTailUpdater, SimpleUpdater,
                       SquaredL2Updater, Updater)
@@ -166,26 +166,13 @@ class MultiTaskGradient(Gradient):
         """Padded margins [n*KC] of the weight block ``v``. ``scoring=True``
         keeps the f32 weights of a bf16 dense shard (split into two bf16
         GEMM operands) where the training route rounds them to bf16."""
-        from ..ops import multiclass as mc
-        from ..ops import multitask as mt
-
         self._check_shard(shard)
-        if shard.kind == "csr":
-            return mc.csr_margins_multi(shard, v, self.num_tasks)
-        pk = mc.packed_copy_for(shard, self.num_tasks)
-        if pk is not None:
-            # W goes in as bf16 hi + lo: one pass serves training and scoring
-            return ops.margins_multi_packed(pk, v, self.num_tasks)
-        if scoring:
-            return mt.dense_margins_scoring(shard.features, v, self.num_tasks)
-        return mc.margins_multi(shard.features, v, self.num_tasks)
+        return mc.multi_margins(shard, v, self.num_tasks, scoring)
 
     def task_losses(self, shard, margins, mask=None, invert=False):
         """(task_loss f64 [R], loss_count f64 [2]) of the local rows from
         padded margins — the loss-only multiplier call; ``invert=True`` sums
         each task's HELD-OUT rows instead of its training rows."""
-        from ..ops import multitask as mt
-
         self._check_shard(shard)
         fold, hold, scale = self._on(margins.device)
         _, task_loss, lc = mt.multiplier_tasks(
@@ -196,8 +183,6 @@ class MultiTaskGradient(Gradient):
     def multiplier_loss(self, shard, margins, mask=None):
         """(padded multiplier flat [n*KC], loss_count) from padded margins —
         the n-space stage (zero data passes)."""
-        from ..ops import multitask as mt
-
         self._check_shard(shard)
         fold, hold, scale = self._on(margins.device)
         m, task_loss, lc = mt.multiplier_tasks(
@@ -207,21 +192,12 @@ class MultiTaskGradient(Gradient):
         return m, lc
 
     def eval_from_margins(self, shard, margins, mask=None, need_grad=True):
-        from ..ops import multiclass as mc
-        from ..ops import multitask as mt
-
         if not need_grad:
             task_loss, lc = self.task_losses(shard, margins, mask)
             self.last_task_loss = task_loss
             return None, lc
         m, lc = self.multiplier_loss(shard, margins, mask)
-        if shard.kind == "csr":
-            return mt.csr_grad_tasks(shard, m, self.num_tasks), lc
-        pk = mc.packed_copy_for(shard, self.num_tasks)
-        if pk is not None:
-            return ops.grad_multi_packed(pk, m, self.num_tasks,
-                                         split_m=True), lc
-        return mt.dense_grad_tasks(shard.features, m, self.num_tasks), lc
+        return mc.multi_grad(shard, m, self.num_tasks), lc
 
     def eval(self, shard, w, mask=None, need_grad=True):
         return self.eval_from_margins(shard, self.margins(shard, w), mask,
@@ -284,8 +260,6 @@ class PerTaskUpdater(Updater):
         return t
 
     def compute(self, weights_old, gradient, step_size, iter, reg_param):  # noqa: A002
-        from ..ops import multitask as mt
-
         if weights_old.numel() % self.num_tasks != 0:
             raise ValueError(
                 f"weights [{weights_old.numel()}] are not a [d, "
@@ -299,8 +273,6 @@ class PerTaskUpdater(Updater):
         ``compute`` takes at ``step`` and the AT interpolation at ``theta``;
         only valid when ``COLUMN_AFFINE_PROX``. The lambdas are the cached
         device vector of ``compute``: the step copies nothing to the device."""
-        from ..ops import multitask as mt
-
         if not self.COLUMN_AFFINE_PROX:
             raise NotImplementedError(
                 f"PerTaskUpdater({type(self.base).__name__}) has no affine prox")

@@ -163,13 +163,11 @@ def grad_multi_packed(pk, m_padded_flat: torch.Tensor, k: int,
     routes use it, because the rounding of M is a gradient error that does
     not shrink near the optimum (it was measured to swallow the restart test
     of a mixed-λ sweep, after which the largest λ's columns diverged)."""
-    from .multiclass import padded_k
+    from .multiclass import padded_k, unpad_columns
 
-    kc = padded_k(k)
-    gradp = _get_hip().grad_multi_packed(pk, m_padded_flat, kc, split_m)
-    if kc != k:
-        return gradp.reshape(pk.d, kc)[:, :k].reshape(-1).contiguous()
-    return gradp
+    gradp = _get_hip().grad_multi_packed(pk, m_padded_flat, padded_k(k),
+                                         split_m)
+    return unpad_columns(gradp, k)
 
 
 # Multi-column passes over a raw fp8 (e4m3fn) dense shard: the MFMA kernels
@@ -201,16 +199,14 @@ def grad_multi_fp8(features: torch.Tensor, m_padded_flat: torch.Tensor, k: int,
                    split_m: bool = False) -> torch.Tensor:
     """grad flat [d*k] = Aᵀ·M on an fp8 shard from the padded multiplier
     [n*KC]; ``split_m`` as in ``grad_multi_packed``."""
-    from .multiclass import padded_k
+    from .multiclass import padded_k, unpad_columns
 
     if not multi_fp8_serves(features, k):
         raise ValueError("grad_multi_fp8 needs a contiguous float8_e4m3fn "
                          "GPU block with d % 16 == 0 and a 16-byte-aligned base")
-    kc = padded_k(k)
-    gradp = _get_hip().grad_multi_fp8(features, m_padded_flat, kc, split_m)
-    if kc != k:
-        return gradp.reshape(features.shape[1], kc)[:, :k].reshape(-1).contiguous()
-    return gradp
+    gradp = _get_hip().grad_multi_fp8(features, m_padded_flat, padded_k(k),
+                                      split_m)
+    return unpad_columns(gradp, k)
 
 
 def dense_pack_decode(pk, out: Optional[torch.Tensor] = None) -> torch.Tensor:

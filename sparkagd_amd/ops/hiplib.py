@@ -874,49 +874,25 @@ def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
     return zm_new, xm_new
 
 
-def dense_eval_multi_from_margins(
-    features: torch.Tensor,
-    margins_padded_flat: torch.Tensor,
-    labels: torch.Tensor,
-    k: int,
-    kc: int,
-    mask: Optional[torch.Tensor] = None,
-    need_grad: bool = True,
-    sample_weight: Optional[torch.Tensor] = None,
-) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
-    from . import multi_fp8_serves
-
+def dense_grad_multi(features: torch.Tensor, m_padded_flat: torch.Tensor,
+                     kc: int) -> torch.Tensor:
+    """Padded gradient flat [d*kc] = Aᵀ·M by the exact-f32 VALU kernel
+    (KC-templated, kc <= 32); row-block partials reduced in fixed order."""
     lib = load()
     n, d = features.shape
-    a_dtype = _DTYPE_CODE[features.dtype]
     dev = features.device
-    M, loss_count = multiplier_multi(margins_padded_flat, labels, k, kc, mask,
-                                     sample_weight)
-    if not need_grad:
-        return None, loss_count
-    algo = os.environ.get("SPARKAGD_MULTI_GRAD", "auto")
-    if features.dtype == torch.bfloat16 and algo in ("auto", "gemm"):
-        # grad = A^T·M as a skinny hipBLASLt TN GEMM — the per-element KC-fma
-        # VALU kernel is issue-bound ~3.5x the A-stream floor
-        # (profiles/r01_multiclass_trace_gemm.txt). Multipliers round to bf16
-        # (standard mixed precision; A is bf16, accumulation f32);
-        # SPARKAGD_MULTI_GRAD=valu selects the exact-f32-multiplier kernel.
-        gradp = gemm_bf16f32_tn(features, M.reshape(n, kc)).reshape(-1)
-    elif algo == "mfma" and multi_fp8_serves(features, k):
-        # opt-in below 33 columns: the fp8 MFMA kernel, M as bf16 hi + lo
-        gradp = grad_multi_fp8(features, M, kc, split_m=True)
-    else:
-        n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
-        gradp = torch.empty(d * kc, dtype=torch.float32, device=dev)
-        part = torch.empty(n_rb * d * kc, dtype=torch.float32, device=dev) if n_rb > 1 else gradp
-        rc = lib.agd_grad_multi(_ptr(features), a_dtype, _ptr(M), n, d, kc,
-                                _ptr(part), n_rb, _ptr(gradp), _stream(features))
-        _check(rc)
-    if kc != k:
-        grad = gradp.reshape(d, kc)[:, :k].reshape(-1).contiguous()
-    else:
-        grad = gradp
-    return grad, loss_count
+    if m_padded_flat.numel() != n * kc:
+        raise TypeError(f"multiplier must be the [n*kc] flat, got "
+                        f"[{m_padded_flat.numel()}] for n={n} kc={kc}")
+    n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
+    gradp = torch.empty(d * kc, dtype=torch.float32, device=dev)
+    part = (torch.empty(n_rb * d * kc, dtype=torch.float32, device=dev)
+            if n_rb > 1 else gradp)
+    _check(lib.agd_grad_multi(
+        _ptr(features), _DTYPE_CODE[features.dtype],
+        _ptr(m_padded_flat.contiguous()), n, d, kc, _ptr(part), n_rb,
+        _ptr(gradp), _stream(features)))
+    return gradp
 
 
 def csr_margins_multi(rowptr, col, val, wflat: torch.Tensor, k: int,

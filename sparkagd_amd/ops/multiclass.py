@@ -20,11 +20,14 @@ operators act elementwise on the flattened weights).
 
 from __future__ import annotations
 
+import os
 from typing import Optional, Tuple
 
 import torch
 
-from . import _use_hip, reference as _ref  # noqa: F401  (dispatch helper)
+from . import (_use_hip, grad_multi_fp8, grad_multi_packed, hiplib,
+               margins_multi_fp8, margins_multi_packed, multi_fp8_serves,
+               multi_packed_serves, reference as _ref)
 
 
 def _pad_classes(t2d: torch.Tensor, kc: int) -> torch.Tensor:
@@ -34,6 +37,14 @@ def _pad_classes(t2d: torch.Tensor, kc: int) -> torch.Tensor:
     out = torch.zeros((n, kc), dtype=t2d.dtype, device=t2d.device)
     out[:, :k] = t2d
     return out
+
+
+def unpad_columns(gradp: torch.Tensor, k: int) -> torch.Tensor:
+    """Logical flat [d*k] of a padded flat [d*KC] gradient."""
+    kc = padded_k(k)
+    if kc == k:
+        return gradp
+    return gradp.reshape(-1, kc)[:, :k].reshape(-1).contiguous()
 
 
 def padded_k(k: int) -> int:
@@ -159,6 +170,53 @@ def ref_csr_grad_multi(rowptr, col, val, m2d: torch.Tensor, d: int) -> torch.Ten
 
 # --- dispatch (GPU -> HIP kernels via hiplib; CPU -> oracle) ---
 
+MULTI_ALGOS = ("auto", "gemm", "valu", "mfma")
+
+
+def dense_multi_route(dtype: torch.dtype, kc: int, fp8_served: bool,
+                      algo: str) -> str:
+    """Backend of a multi-column data pass over a raw dense GPU block, for
+    the margins Z = A·W and the gradient G = Aᵀ·M alike (the table of
+    docs/KERNELS.md, first match wins):
+
+      "gemm"      bf16 unless ``algo == "valu"``: hipBLASLt, the f32 operand
+                  (W or M) rounded to bf16
+      "mm"        f32 above 32 padded columns: rocBLAS through torch
+      "fp8_mfma"  ``fp8_served`` (``multi_fp8_serves``) above 32 padded
+                  columns, or at any width under ``algo == "mfma"``
+      "valu"      the KC-templated exact-f32 kernels, ``kc <= 32``
+
+    ``algo`` is the value of SPARKAGD_MULTI_MARGINS / SPARKAGD_MULTI_GRAD.
+    "mfma" is defined for fp8 shards only; on any other block it means
+    "auto". Pure: no tensor and no library is touched."""
+    if algo not in MULTI_ALGOS:
+        raise ValueError(
+            f"SPARKAGD_MULTI_MARGINS / SPARKAGD_MULTI_GRAD must be one of "
+            f"{', '.join(MULTI_ALGOS)}; got {algo!r}")
+    if dtype == torch.bfloat16 and algo != "valu":
+        return "gemm"
+    if dtype == torch.float32 and kc > 32:
+        return "mm"
+    if fp8_served and (kc > 32 or algo == "mfma"):
+        return "fp8_mfma"
+    if kc <= 32:
+        # VALU kernels are KC-templated <= 32
+        return "valu"
+    raise NotImplementedError(
+        f"no multi-column kernel for KC={kc} > 32 on this {dtype} block under "
+        f"algo={algo}: use a bf16 shard (hipBLASLt GEMM), an f32 shard "
+        "(rocBLAS) or an fp8 shard with d % 16 == 0 (MFMA kernels)")
+
+
+def _dense_route(features: torch.Tensor, k: int, grad: bool) -> str:
+    """``dense_multi_route`` of a feature block; the one place that reads
+    the two environment variables."""
+    algo = (os.environ.get("SPARKAGD_MULTI_GRAD", "auto") if grad
+            else os.environ.get("SPARKAGD_MULTI_MARGINS", "auto"))
+    return dense_multi_route(features.dtype, padded_k(k),
+                             multi_fp8_serves(features, k), algo)
+
+
 def _gemm_margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int,
                         kc: int) -> torch.Tensor:
     """Margins as a skinny hipBLASLt GEMM: Z[n,KC] = A[n,d]·bf16(W)[d,KC].
@@ -169,8 +227,6 @@ def _gemm_margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int,
     bf16 mixed-precision compute path; A is already bf16, accumulation f32);
     SPARKAGD_MULTI_MARGINS=valu selects the exact-f32-weights kernel instead.
     """
-    from . import hiplib
-
     n, d = features.shape
     wt = torch.zeros((kc, d), dtype=torch.bfloat16, device=features.device)
     wt[:k] = wflat.reshape(d, k).T.to(torch.bfloat16)
@@ -179,114 +235,100 @@ def _gemm_margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int,
     return z.reshape(-1)
 
 
-def margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int) -> torch.Tensor:
-    """Flat padded margins [n*KC] (opaque to callers; feed back into
-    eval_multi_from_margins / axpby for margin tracking)."""
-    import os
-
-    kc = padded_k(k)
-    if _use_hip(features):
-        from . import hiplib, margins_multi_fp8, multi_fp8_serves
-
-        algo = os.environ.get("SPARKAGD_MULTI_MARGINS", "auto")
-        if kc > 32:
-            # VALU kernels are KC-templated <= 32; large K runs GEMM-shaped
-            if features.dtype == torch.bfloat16 and algo != "valu":
-                return _gemm_margins_multi(features, wflat, k, kc)
-            if features.dtype == torch.float32:
-                # rocBLAS via torch.mm is the idiomatic f32 library GEMM
-                z = features @ wflat.reshape(features.shape[1], k).to(torch.float32)
-                return _pad_classes(z, kc).reshape(-1)
-            if multi_fp8_serves(features, k):
-                return margins_multi_fp8(features, wflat, k)
-            raise NotImplementedError(
-                f"K={k} > 32 margins need a bf16 (hipBLASLt) or f32 (rocBLAS) "
-                "shard, or an fp8 shard with d % 16 == 0 (MFMA kernel)")
-        if features.dtype == torch.bfloat16 and algo in ("auto", "gemm"):
-            return _gemm_margins_multi(features, wflat, k, kc)
-        if algo == "mfma" and multi_fp8_serves(features, k):
-            return margins_multi_fp8(features, wflat, k)
-        return hiplib.dense_margins_multi(features, wflat, k, kc)
-    z = ref_margins_multi(features, wflat, k).reshape(features.shape[0], k)
-    return _pad_classes(z, kc).reshape(-1)
-
-
-def _eval_large_k_from_margins(features, margins_padded_flat, labels, k, kc,
-                               mask, need_grad, sample_weight):
-    """K > 32 path: the generic-K multiplier kernel (wave-per-row
-    k_multiplier_multi_anyk — ONE launch instead of the ~6-kernel torch
-    stage this replaced in round 1), then grad as the hipBLASLt TN GEMM
-    (bf16 shards, padded M fed straight in — its pad columns are exact
-    zeros) or rocBLAS torch.mm (f32 shards)."""
-    import os
-
-    from . import hiplib
-
+def _gemm_margins_scoring(features: torch.Tensor, wflat: torch.Tensor, k: int,
+                          kc: int) -> torch.Tensor:
+    """Margins of a bf16 block for SCORING returned weights. The training
+    GEMM rounds W to bf16, a 2^-9 relative change of every weight: harmless
+    inside the iteration, but a score must belong to the weights the caller
+    gets back. Here W goes in as bf16(W) + bf16(W - bf16(W)), two
+    accumulating hipBLASLt GEMMs (2^-17 per weight) at about twice the
+    one-GEMM cost — the exact-f32 VALU kernel would cost ~12 A-streams.
+    Every other route already multiplies the exact weights (the MFMA kernels
+    carry W as bf16 hi + lo)."""
     n, d = features.shape
-    M, loss_count = hiplib.multiplier_multi(margins_padded_flat, labels, k, kc,
-                                            mask, sample_weight)
-    if not need_grad:
-        return None, loss_count
-    if (features.dtype == torch.bfloat16
-            and os.environ.get("SPARKAGD_MULTI_GRAD", "auto") != "valu"):
-        grad = hiplib.gemm_bf16f32_tn(features, M.reshape(n, kc))
-        return grad.reshape(d, kc)[:, :k].reshape(-1).contiguous(), loss_count
-    if features.dtype == torch.float32:
-        m = M.reshape(n, kc)[:, :k]
-        return (features.T @ m).reshape(-1), loss_count
-    from . import grad_multi_fp8, multi_fp8_serves
+    wt = torch.zeros((kc, d), dtype=torch.float32, device=features.device)
+    wt[:k] = wflat.reshape(d, k).T
+    hi = wt.to(torch.bfloat16)
+    lo = (wt - hi.to(torch.float32)).to(torch.bfloat16)
+    z = torch.empty((n, kc), dtype=torch.float32, device=features.device)
+    hiplib.gemm_bf16f32_nt(features, hi, z)
+    hiplib.gemm_bf16f32_nt(features, lo, z, beta=1.0)
+    return z.reshape(-1)
 
-    if multi_fp8_serves(features, k):
-        return grad_multi_fp8(features, M, k, split_m=True), loss_count
-    raise NotImplementedError(
-        f"K={k} > 32 gradient needs a bf16 (hipBLASLt) or f32 (rocBLAS) shard, "
-        "or an fp8 shard with d % 16 == 0 (MFMA kernel)")
+
+def margins_multi(features: torch.Tensor, wflat: torch.Tensor, k: int,
+                  scoring: bool = False) -> torch.Tensor:
+    """Flat padded margins [n*KC] of a dense block (opaque to callers; feed
+    back into eval_multi_from_margins / axpby for margin tracking).
+    ``scoring=True`` keeps the f32 weights of a bf16 GPU block
+    (``_gemm_margins_scoring``)."""
+    kc = padded_k(k)
+    if not _use_hip(features):
+        z = ref_margins_multi(features, wflat, k).reshape(features.shape[0], k)
+        return _pad_classes(z, kc).reshape(-1)
+    if scoring and features.dtype == torch.bfloat16:
+        return _gemm_margins_scoring(features, wflat, k, kc)
+    route = _dense_route(features, k, grad=False)
+    if route == "gemm":
+        return _gemm_margins_multi(features, wflat, k, kc)
+    if route == "mm":
+        # rocBLAS via torch.mm is the idiomatic f32 library GEMM
+        z = features @ wflat.reshape(features.shape[1], k).to(torch.float32)
+        return _pad_classes(z, kc).reshape(-1)
+    if route == "fp8_mfma":
+        return margins_multi_fp8(features, wflat, k)
+    return hiplib.dense_margins_multi(features, wflat, k, kc)
+
+
+def grad_from_mult_multi(features, m_padded_flat, k):
+    """grad flat [d*k] = Aᵀ·M of a dense block from the padded multiplier."""
+    kc = padded_k(k)
+    n = features.shape[0]
+    if not _use_hip(features):
+        acc = (torch.float32 if features.dtype in
+               (torch.bfloat16, torch.float16, torch.float8_e4m3fn)
+               else features.dtype)
+        m = m_padded_flat.reshape(n, kc)[:, :k].to(acc)
+        return (features.to(acc).T @ m).reshape(-1)
+    route = _dense_route(features, k, grad=True)
+    if route == "gemm":
+        # the per-element KC-fma VALU kernel is issue-bound ~3.5x the
+        # A-stream floor (profiles/r01_multiclass_trace_gemm.txt). The
+        # multipliers round to bf16 (standard mixed precision; A is bf16,
+        # accumulation f32) and the pad columns of M are exact zeros;
+        # SPARKAGD_MULTI_GRAD=valu selects the exact-f32-multiplier kernel.
+        gradp = hiplib.gemm_bf16f32_tn(features, m_padded_flat.reshape(n, kc))
+        return unpad_columns(gradp.reshape(-1), k)
+    if route == "mm":
+        return (features.T @ m_padded_flat.reshape(n, kc)[:, :k]).reshape(-1)
+    if route == "fp8_mfma":
+        # M as a bf16 hi + lo pair
+        return grad_multi_fp8(features, m_padded_flat, k, split_m=True)
+    return unpad_columns(hiplib.dense_grad_multi(features, m_padded_flat, kc), k)
+
+
+def multiplier_loss_multi(labels, margins_padded_flat, k, mask=None,
+                          sample_weight=None):
+    """(M padded flat [n*KC] with exact-zero pad columns, loss_count f64[2])
+    from padded margins — the n-space softmax stage, zero data passes (one
+    kernel for every KC: templated <= 32, generic wave-per-row above)."""
+    kc = padded_k(k)
+    if _use_hip(margins_padded_flat):
+        return hiplib.multiplier_multi(margins_padded_flat, labels, k, kc,
+                                       mask, sample_weight)
+    n = margins_padded_flat.numel() // kc
+    z = margins_padded_flat.reshape(n, kc)[:, :k]
+    m, lc = ref_multiplier_multi(z, labels, mask, sample_weight)
+    return _pad_classes(m, kc).reshape(-1), lc
 
 
 def eval_multi_from_margins(features, margins_padded_flat, labels, k,
                             mask=None, need_grad=True, sample_weight=None):
-    kc = padded_k(k)
-    if _use_hip(features):
-        from . import hiplib
-
-        if kc > 32:
-            return _eval_large_k_from_margins(
-                features, margins_padded_flat, labels, k, kc, mask, need_grad,
-                sample_weight)
-        return hiplib.dense_eval_multi_from_margins(
-            features, margins_padded_flat, labels, k, kc, mask, need_grad,
-            sample_weight)
-    n = features.shape[0]
-    z = margins_padded_flat.reshape(n, kc)[:, :k].reshape(-1)
-    grad, lc = ref_eval_multi_from_margins(z, labels, features, k, mask,
-                                           need_grad, sample_weight)
-    return grad, lc
-
-
-def packed_copy_for(shard, k: int):
-    """The shard's packed copy when the packed multi-column kernels serve it
-    (a dense shard that already is packed, on the GPU, padded_k(k) <= 128),
-    else None: the caller keeps the raw route."""
-    from . import multi_packed_serves
-
-    if getattr(shard, "kind", None) != "dense":
-        return None
-    pk = shard._packed_gpu()
-    return pk if multi_packed_serves(pk, k) else None
-
-
-def eval_multi_packed_from_margins(pk, margins_padded_flat, labels, k,
-                                   mask=None, need_grad=True,
-                                   sample_weight=None):
-    """``eval_multi_from_margins`` on a packed copy: the multiplier kernel,
-    then Aᵀ·M by the packed MFMA gradient kernel."""
-    from . import grad_multi_packed
-
     M, loss_count = multiplier_loss_multi(labels, margins_padded_flat, k, mask,
                                           sample_weight)
     if not need_grad:
         return None, loss_count
-    return grad_multi_packed(pk, M, k, split_m=True), loss_count
+    return grad_from_mult_multi(features, M, k), loss_count
 
 
 def eval_multi(features, labels, wflat, k, mask=None, need_grad=True,
@@ -296,149 +338,105 @@ def eval_multi(features, labels, wflat, k, mask=None, need_grad=True,
                                    sample_weight)
 
 
-# --- CSR dispatch ---
+# --- CSR shards ---
 
 def csr_margins_multi(shard, wflat: torch.Tensor, k: int) -> torch.Tensor:
     """Flat padded margins [n*KC] over a CSRShard. K > 32 runs the KC=32
     gather kernel per 32-class chunk (the nnz stream re-reads per chunk —
     the K-proportional W/M traffic dominates anyway)."""
     kc = padded_k(k)
-    if _use_hip(shard.val):
-        from . import hiplib
-
-        if kc <= 32:
-            return hiplib.csr_margins_multi(shard.rowptr, shard.col, shard.val,
-                                            wflat, k, kc, shard.d)
-        n, d = shard.n, shard.d
-        w2 = wflat.reshape(d, k).to(torch.float32)
-        z = torch.zeros((n, kc), dtype=torch.float32, device=shard.val.device)
-        for lo in range(0, k, 32):
-            hi = min(lo + 32, k)
-            wc = w2[:, lo:hi]
-            zc = hiplib.csr_margins_multi(shard.rowptr, shard.col, shard.val,
-                                          wc.reshape(-1), hi - lo,
-                                          padded_k(hi - lo), d)
-            z[:, lo:hi] = zc.reshape(n, padded_k(hi - lo))[:, : hi - lo]
-        return z.reshape(-1)
-    z = ref_csr_margins_multi(shard.rowptr, shard.col, shard.val, wflat, k,
-                              shard.d).reshape(-1, k)
-    return _pad_classes(z, kc).reshape(-1)
+    if not _use_hip(shard.val):
+        z = ref_csr_margins_multi(shard.rowptr, shard.col, shard.val, wflat, k,
+                                  shard.d).reshape(-1, k)
+        return _pad_classes(z, kc).reshape(-1)
+    if kc <= 32:
+        return hiplib.csr_margins_multi(shard.rowptr, shard.col, shard.val,
+                                        wflat, k, kc, shard.d)
+    n, d = shard.n, shard.d
+    w2 = wflat.reshape(d, k).to(torch.float32)
+    z = torch.zeros((n, kc), dtype=torch.float32, device=shard.val.device)
+    for lo in range(0, k, 32):
+        hi = min(lo + 32, k)
+        wc = w2[:, lo:hi]
+        zc = hiplib.csr_margins_multi(shard.rowptr, shard.col, shard.val,
+                                      wc.reshape(-1), hi - lo,
+                                      padded_k(hi - lo), d)
+        z[:, lo:hi] = zc.reshape(n, padded_k(hi - lo))[:, : hi - lo]
+    return z.reshape(-1)
 
 
-def eval_multi_csr_from_margins(shard, margins_padded_flat, k,
-                                mask=None, need_grad=True, sample_weight=None):
+def csr_grad_multi(shard, m_padded_flat: torch.Tensor, k: int) -> torch.Tensor:
+    """grad flat [d*k] = Aᵀ·M on a CSRShard from the padded multiplier: the
+    deterministic CSC gather (k_csc_grad_multi; 32-column chunks above
+    KC = 32), the index_add oracle on CPU."""
     kc = padded_k(k)
     n = shard.n
-    if _use_hip(shard.val):
-        from . import hiplib
-
-        # the multiplier kernel covers every KC (templated <= 32, generic
-        # wave-per-row above)
-        M, lc = hiplib.multiplier_multi(margins_padded_flat, shard.labels,
-                                        k, kc, mask, sample_weight)
-        if not need_grad:
-            return None, lc
-        if shard.csc is None:
-            raise RuntimeError(
-                "CSR multiclass gradient needs the deterministic CSC copy "
-                "(CSRShard(..., deterministic=True))")
-        colptr, crow, cval = shard.csc
-        if kc <= 32:
-            gradp = hiplib.csc_grad_multi(colptr, crow, cval, M, shard.d, kc,
-                                          getattr(shard, 'csc_heavy', None))
-            if kc != k:
-                return gradp.reshape(shard.d, kc)[:, :k].reshape(-1).contiguous(), lc
-            return gradp, lc
-        m2d = M.reshape(n, kc)[:, :k]
-        grad = torch.empty((shard.d, k), dtype=torch.float32,
-                           device=shard.val.device)
-        for lo in range(0, k, 32):
-            hi = min(lo + 32, k)
-            kcc = padded_k(hi - lo)
-            mc_chunk = torch.zeros((n, kcc), dtype=torch.float32,
-                                   device=shard.val.device)
-            mc_chunk[:, : hi - lo] = m2d[:, lo:hi]
-            gc = hiplib.csc_grad_multi(colptr, crow, cval,
-                                       mc_chunk.reshape(-1), shard.d, kcc,
-                                       getattr(shard, 'csc_heavy', None))
-            grad[:, lo:hi] = gc.reshape(shard.d, kcc)[:, : hi - lo]
-        return grad.reshape(-1).contiguous(), lc
-    z = margins_padded_flat.reshape(n, kc)[:, :k]
-    m, lc = ref_multiplier_multi(z, shard.labels, mask, sample_weight)
-    if not need_grad:
-        return None, lc
-    return ref_csr_grad_multi(shard.rowptr, shard.col, shard.val, m, shard.d), lc
+    if not _use_hip(shard.val):
+        m = m_padded_flat.reshape(n, kc)[:, :k]
+        return ref_csr_grad_multi(shard.rowptr, shard.col, shard.val, m, shard.d)
+    if shard.csc is None:
+        raise RuntimeError(
+            "the CSR multi-column gradient needs the deterministic CSC copy "
+            "(CSRShard(..., deterministic=True))")
+    colptr, crow, cval = shard.csc
+    heavy = getattr(shard, "csc_heavy", None)
+    if kc <= 32:
+        return unpad_columns(
+            hiplib.csc_grad_multi(colptr, crow, cval, m_padded_flat, shard.d,
+                                  kc, heavy), k)
+    m2d = m_padded_flat.reshape(n, kc)[:, :k]
+    grad = torch.empty((shard.d, k), dtype=torch.float32,
+                       device=shard.val.device)
+    for lo in range(0, k, 32):
+        hi = min(lo + 32, k)
+        kcc = padded_k(hi - lo)
+        chunk = torch.zeros((n, kcc), dtype=torch.float32,
+                            device=shard.val.device)
+        chunk[:, : hi - lo] = m2d[:, lo:hi]
+        gc = hiplib.csc_grad_multi(colptr, crow, cval, chunk.reshape(-1),
+                                   shard.d, kcc, heavy)
+        grad[:, lo:hi] = gc.reshape(shard.d, kcc)[:, : hi - lo]
+    return grad.reshape(-1).contiguous()
 
 
-def eval_multi_csr(shard, wflat, k, mask=None, need_grad=True,
-                   sample_weight=None):
-    zf = csr_margins_multi(shard, wflat, k)
-    return eval_multi_csr_from_margins(shard, zf, k, mask, need_grad,
-                                       sample_weight)
+# --- the two data passes of a shard (softmax and multi-task alike) ---
+
+def packed_copy_for(shard, k: int):
+    """The shard's packed copy when the packed multi-column kernels serve it
+    (a dense shard that already is packed, on the GPU, padded_k(k) <= 128),
+    else None: the caller keeps the raw route."""
+    if getattr(shard, "kind", None) != "dense":
+        return None
+    pk = shard._packed_gpu()
+    return pk if multi_packed_serves(pk, k) else None
 
 
-# --- n-space pieces for the Gram (dual-space) solver ---
-
-def multiplier_loss_multi(labels, margins_padded_flat, k, mask=None,
-                          sample_weight=None):
-    """(M padded flat [n*KC] with exact-zero pad columns, loss_count f64[2])
-    from padded margins — zero data passes; the multiclass analog of
-    ops.dense_multiplier_loss for the Gram solver."""
-    kc = padded_k(k)
-    n = margins_padded_flat.numel() // kc
-    if margins_padded_flat.is_cuda:
-        import os
-
-        if os.environ.get("SPARKAGD_FORCE_REFERENCE") != "1":
-            from . import hiplib
-
-            return hiplib.multiplier_multi(margins_padded_flat, labels, k, kc,
-                                           mask, sample_weight)
-    z = margins_padded_flat.reshape(n, kc)[:, :k]
-    m, lc = ref_multiplier_multi(z, labels, mask, sample_weight)
-    return _pad_classes(m, kc).reshape(-1), lc
+def multi_margins(shard, v: torch.Tensor, k: int,
+                  scoring: bool = False) -> torch.Tensor:
+    """Flat padded margins [n*KC] = A·V of a shard's rows for the [d, k]
+    block ``v``: the CSR gather, the packed copy's MFMA kernel when it
+    serves, else the raw dense block by ``dense_multi_route``. ``scoring``
+    as in ``margins_multi``; CSR and packed passes carry the exact f32
+    weights anyway (packed: W as bf16 hi + lo, one pass serves training and
+    scoring)."""
+    if getattr(shard, "kind", None) == "csr":
+        return csr_margins_multi(shard, v, k)
+    pk = packed_copy_for(shard, k)
+    if pk is not None:
+        return margins_multi_packed(pk, v, k)
+    return margins_multi(shard.features, v, k, scoring)
 
 
-def grad_from_mult_multi(features, m_padded_flat, k):
-    """grad flat [d*k] = Aᵀ·M from the padded multiplier (dense shards)."""
-    kc = padded_k(k)
-    n, d = features.shape
-    if _use_hip(features):
-        import os
-
-        from . import grad_multi_fp8, hiplib, multi_fp8_serves
-
-        algo = os.environ.get("SPARKAGD_MULTI_GRAD", "auto")
-        if features.dtype == torch.bfloat16 and algo != "valu":
-            gradp = hiplib.gemm_bf16f32_tn(
-                features, m_padded_flat.reshape(n, kc)).reshape(-1)
-        elif (kc > 32 or algo == "mfma") and multi_fp8_serves(features, k):
-            return grad_multi_fp8(features, m_padded_flat, k, split_m=True)
-        else:
-            if kc > 32:
-                raise NotImplementedError(
-                    "K > 32 VALU grad unsupported — bf16 shards use the GEMM, "
-                    "fp8 shards with d % 16 == 0 the MFMA kernel")
-            lib = hiplib.load()
-            n_rb = int(lib.agd_multi_rowblocks(n, d, kc))
-            gradp = torch.empty(d * kc, dtype=torch.float32,
-                                device=features.device)
-            part = (torch.empty(n_rb * d * kc, dtype=torch.float32,
-                                device=features.device)
-                    if n_rb > 1 else gradp)
-            rc = lib.agd_grad_multi(hiplib._ptr(features),
-                                    hiplib._DTYPE_CODE[features.dtype],
-                                    hiplib._ptr(m_padded_flat.contiguous()),
-                                    n, d, kc, hiplib._ptr(part), n_rb,
-                                    hiplib._ptr(gradp),
-                                    hiplib._stream(features))
-            hiplib._check(rc)
-        if kc != k:
-            return gradp.reshape(d, kc)[:, :k].reshape(-1).contiguous()
-        return gradp
-    acc = torch.float32 if features.dtype in (torch.bfloat16, torch.float16) else features.dtype
-    m = m_padded_flat.reshape(n, kc)[:, :k].to(acc)
-    return (features.to(acc).T @ m).reshape(-1)
+def multi_grad(shard, m_padded_flat: torch.Tensor, k: int) -> torch.Tensor:
+    """grad flat [d*k] = Aᵀ·M of a shard's rows from the padded multiplier
+    [n*KC]; the ladder of ``multi_margins``. The packed kernel takes M as a
+    bf16 hi + lo pair (``ops.grad_multi_packed`` says why)."""
+    if getattr(shard, "kind", None) == "csr":
+        return csr_grad_multi(shard, m_padded_flat, k)
+    pk = packed_copy_for(shard, k)
+    if pk is not None:
+        return grad_multi_packed(pk, m_padded_flat, k, split_m=True)
+    return grad_from_mult_multi(shard.features, m_padded_flat, k)
 
 
 def multiclass_metrics(margins_padded_flat, labels, k, sample_weight=None):
@@ -447,9 +445,8 @@ def multiclass_metrics(margins_padded_flat, labels, k, sample_weight=None):
     ``reference.multiclass_metrics`` on CPU."""
     kc = padded_k(k)
     if _use_hip(margins_padded_flat):
-        from . import hiplib
-
         return hiplib.multiclass_metrics(margins_padded_flat, labels, k, kc,
                                          sample_weight)
     return _ref.multiclass_metrics(margins_padded_flat, labels, k, kc,
                                    sample_weight)
+

@@ -28,8 +28,8 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _use_hip, reference as _ref
-from .multiclass import _pad_classes, padded_k, ref_csr_grad_multi
+from . import _use_hip, hiplib, reference as _ref
+from .multiclass import _pad_classes, padded_k
 
 
 # --- oracle (plain torch; CPU tier + GPU-kernel ground truth) ---
@@ -160,8 +160,6 @@ def multiplier_tasks(
     loss-only call (no M is written)."""
     kc = padded_k(num_tasks)
     if _use_hip(margins_padded_flat):
-        from . import hiplib
-
         return hiplib.multiplier_tasks(
             margins_padded_flat, labels, loss_type, num_tasks, kc, task_scale,
             mask, sample_weight, fold_id, holdout, invert, need_mult)
@@ -181,8 +179,6 @@ def prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
     """One proximal step of every task + the summed regularisation value;
     ``lam`` / ``lam2`` are [R] (f64)."""
     if _use_hip(w):
-        from . import hiplib
-
         return hiplib.prox_tasks(kind, w, g, step, lam, lam2)
     return ref_prox_tasks(kind, w, g, step, lam, lam2)
 
@@ -198,94 +194,9 @@ def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
     if lam.numel() != num_tasks:
         raise ValueError(f"lam has {lam.numel()} entries for {num_tasks} tasks")
     if _use_hip(zm_old):
-        from . import hiplib
-
         return hiplib.at_margin_update_tasks(zm_old, xm_old, gm, step, lam,
                                              theta, num_tasks,
                                              padded_k(num_tasks))
     return ref_at_margin_update_tasks(zm_old, xm_old, gm, step, lam, theta,
                                       num_tasks)
 
-
-def dense_margins_scoring(features: torch.Tensor, wflat: torch.Tensor,
-                          k: int) -> torch.Tensor:
-    """Flat padded margins [n*KC] for SCORING returned weights. The training
-    route of a bf16 shard (``multiclass.margins_multi``) rounds W to bf16 for
-    its GEMM, a 2^-9 relative change of every weight: harmless inside the
-    iteration, but a score must belong to the weights the caller gets back.
-    Here W goes in as bf16(W) + bf16(W - bf16(W)), two accumulating
-    hipBLASLt GEMMs (2^-17 per weight) at about twice the one-GEMM cost — the
-    exact-f32 VALU kernel would cost ~12 A-streams. Every other shard dtype
-    already multiplies the exact weights (an fp8 shard with more than 32
-    columns through ``margins_multi_fp8``, W as bf16 hi + lo)."""
-    from .multiclass import margins_multi
-
-    if not (_use_hip(features) and features.dtype == torch.bfloat16):
-        return margins_multi(features, wflat, k)
-    from . import hiplib
-
-    kc = padded_k(k)
-    n, d = features.shape
-    wt = torch.zeros((kc, d), dtype=torch.float32, device=features.device)
-    wt[:k] = wflat.reshape(d, k).T
-    hi = wt.to(torch.bfloat16)
-    lo = (wt - hi.to(torch.float32)).to(torch.bfloat16)
-    z = torch.empty((n, kc), dtype=torch.float32, device=features.device)
-    hiplib.gemm_bf16f32_nt(features, hi, z)
-    hiplib.gemm_bf16f32_nt(features, lo, z, beta=1.0)
-    return z.reshape(-1)
-
-
-def dense_grad_tasks(features: torch.Tensor, m_padded_flat: torch.Tensor,
-                     k: int) -> torch.Tensor:
-    """grad flat [d*k] = Aᵀ·M on a dense shard: ``grad_from_mult_multi``,
-    plus the rocBLAS route the multinomial path takes for an f32 shard with
-    more than 32 columns (no VALU kernel above the KC=32 template). An fp8
-    shard with more than 32 columns runs the MFMA kernel ``k_grad_multi_f8``
-    (inside ``grad_from_mult_multi``; M as a bf16 hi + lo pair)."""
-    from .multiclass import grad_from_mult_multi
-
-    kc = padded_k(k)
-    if (_use_hip(features) and kc > 32
-            and features.dtype == torch.float32):
-        n = features.shape[0]
-        return (features.T @ m_padded_flat.reshape(n, kc)[:, :k]).reshape(-1)
-    return grad_from_mult_multi(features, m_padded_flat, k)
-
-
-def csr_grad_tasks(shard, m_padded_flat: torch.Tensor, k: int) -> torch.Tensor:
-    """grad flat [d*k] = Aᵀ·M on a CSR shard from the padded multiplier: the
-    deterministic CSC gather (k_csc_grad_multi; 32-column chunks above
-    KC = 32), the index_add oracle on CPU."""
-    kc = padded_k(k)
-    n = shard.n
-    if not _use_hip(shard.val):
-        m = m_padded_flat.reshape(n, kc)[:, :k]
-        return ref_csr_grad_multi(shard.rowptr, shard.col, shard.val, m, shard.d)
-    from . import hiplib
-
-    if shard.csc is None:
-        raise RuntimeError(
-            "CSR multi-task gradient needs the deterministic CSC copy "
-            "(CSRShard(..., deterministic=True))")
-    colptr, crow, cval = shard.csc
-    heavy = getattr(shard, "csc_heavy", None)
-    if kc <= 32:
-        gradp = hiplib.csc_grad_multi(colptr, crow, cval, m_padded_flat,
-                                      shard.d, kc, heavy)
-        if kc != k:
-            return gradp.reshape(shard.d, kc)[:, :k].reshape(-1).contiguous()
-        return gradp
-    m2d = m_padded_flat.reshape(n, kc)[:, :k]
-    grad = torch.empty((shard.d, k), dtype=torch.float32,
-                       device=shard.val.device)
-    for lo in range(0, k, 32):
-        hi = min(lo + 32, k)
-        kcc = padded_k(hi - lo)
-        chunk = torch.zeros((n, kcc), dtype=torch.float32,
-                            device=shard.val.device)
-        chunk[:, : hi - lo] = m2d[:, lo:hi]
-        gc = hiplib.csc_grad_multi(colptr, crow, cval, chunk.reshape(-1),
-                                   shard.d, kcc, heavy)
-        grad[:, lo:hi] = gc.reshape(shard.d, kcc)[:, : hi - lo]
-    return grad.reshape(-1).contiguous()
