@@ -221,6 +221,16 @@ def _prep_weights(sw: Optional[torch.Tensor], device) -> Optional[torch.Tensor]:
     return sw.contiguous().to(device)
 
 
+def _empty_shard_eval(features: torch.Tensor, need_grad: bool = True):
+    """(grad, loss_count) of a shard without rows, returned before any
+    launch: a zero gradient (what this rank adds to the all-reduce) and
+    loss_count = (0, 0)."""
+    acc = _ACC_DTYPE[features.dtype]
+    dev = features.device
+    grad = torch.zeros(features.shape[1], dtype=acc, device=dev) if need_grad else None
+    return grad, torch.zeros(2, dtype=torch.float64, device=dev)
+
+
 def dense_eval(
     features: torch.Tensor,
     labels: torch.Tensor,
@@ -230,9 +240,11 @@ def dense_eval(
     need_grad: bool = True,
     sample_weight: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    n, d = features.shape
+    if n == 0:
+        return _empty_shard_eval(features, need_grad)
     lib = load()
     assert features.is_cuda and features.is_contiguous() and features.ndim == 2
-    n, d = features.shape
     a_dtype = _DTYPE_CODE[features.dtype]
     acc = _ACC_DTYPE[features.dtype]
     if w.dtype != acc:
@@ -272,9 +284,12 @@ def dense_eval(
 
 def dense_margins(features: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """margins = A @ v for an arbitrary d-vector (margin-state tracking)."""
+    n, d = features.shape
+    if n == 0:  # no rows: empty margins, nothing to launch
+        return torch.empty(0, dtype=_ACC_DTYPE[features.dtype],
+                           device=features.device)
     lib = load()
     assert features.is_cuda and features.is_contiguous() and features.ndim == 2
-    n, d = features.shape
     a_dtype = _DTYPE_CODE[features.dtype]
     acc = _ACC_DTYPE[features.dtype]
     if v.dtype != acc:
@@ -302,9 +317,11 @@ def dense_eval_from_margins(
     sample_weight: Optional[torch.Tensor] = None,
 ) -> Tuple[Optional[torch.Tensor], torch.Tensor]:
     """multiplier/loss (+ A^T·m when need_grad) from precomputed margins."""
+    n, d = features.shape
+    if n == 0:
+        return _empty_shard_eval(features, need_grad)
     lib = load()
     assert features.is_cuda and features.is_contiguous() and features.ndim == 2
-    n, d = features.shape
     a_dtype = _DTYPE_CODE[features.dtype]
     acc = _ACC_DTYPE[features.dtype]
     assert margins.dtype == acc and margins.numel() == n
@@ -371,8 +388,10 @@ def dense_multiplier_loss(
 def dense_grad_from_mult(features: torch.Tensor, mult: torch.Tensor) -> torch.Tensor:
     """A^T @ mult for an arbitrary multiplier vector (Gram solver's final
     weight materialization)."""
-    lib = load()
     n, d = features.shape
+    if n == 0:
+        return _empty_shard_eval(features)[0]
+    lib = load()
     a_dtype = _DTYPE_CODE[features.dtype]
     acc = _ACC_DTYPE[features.dtype]
     assert mult.dtype == acc and mult.numel() == n

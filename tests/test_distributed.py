@@ -412,6 +412,9 @@ def _env_worker(rank, world, port, out_q):
     os.environ["WORLD_SIZE"] = str(world)
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    # the ranks reduce a CPU tensor: on a GPU machine the default backend
+    # would be RCCL, which takes no CPU tensors (and no two ranks on one GPU)
+    os.environ["SPARKAGD_DIST_BACKEND"] = "gloo"
     comm = init_from_env()
     try:
         t = torch.full((4,), float(rank + 1), dtype=torch.float64)

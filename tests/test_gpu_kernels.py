@@ -623,7 +623,15 @@ def test_fuzz_csr_eval_random_configs():
         n = [5000, 1701, 12000, 300][cfg]
         d = [2000, 517, 30000, 40][cfg]
         nnz_row = [8, 3, 24, 5][cfg]
-        nnz = n * nnz_row
+        # variable row lengths 0 .. 2*nnz_row (mean nnz_row); every seventh
+        # row and the first and last are empty (rowptr[k] == rowptr[k+1])
+        counts = torch.randint(0, 2 * nnz_row + 1, (n,), generator=g, device=DEV)
+        counts[::7] = 0
+        counts[-1] = 0
+        rowptr = torch.zeros(n + 1, device=DEV, dtype=torch.int32)
+        rowptr[1:] = torch.cumsum(counts, 0)
+        nnz = int(rowptr[-1])
+        rows = torch.repeat_interleave(torch.arange(n, device=DEV), counts)
         if cfg % 2 == 0:  # skewed: 30% of entries in a few hot columns
             hot = torch.randint(0, 3, (nnz,), generator=g, device=DEV)
             uni = torch.randint(0, d, (nnz,), generator=g, device=DEV)
@@ -632,13 +640,12 @@ def test_fuzz_csr_eval_random_configs():
         else:
             col = torch.randint(0, d, (nnz,), generator=g, device=DEV,
                                 dtype=torch.int32)
-        col = col.view(n, nnz_row).sort(dim=1).values.reshape(-1)
+        # columns ascending within each row (duplicates stay)
+        col = (rows * d + col.to(torch.int64)).sort().values.remainder(d).to(torch.int32)
         val = torch.randn(nnz, generator=g, device=DEV)
-        rowptr = torch.arange(0, nnz + 1, nnz_row, device=DEV,
-                              dtype=torch.int32)
-        # punch a few empty rows (rowptr[k] == rowptr[k+1])
         labels = (torch.rand(n, generator=g, device=DEV) < 0.5).float()
         shard = CSRShard(rowptr, col, val, labels, d)
+        assert int((torch.diff(shard.rowptr) == 0).sum()) >= n // 7
         w = torch.randn(d, generator=g, device=DEV) * 0.1
         loss_type = cfg % 4
         gh, lh = shard.eval(w, loss_type)
