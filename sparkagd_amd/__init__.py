@@ -40,7 +40,8 @@ from .models.trainers import (LogisticRegressionWithAGD, LinearRegressionWithAGD
                               SVMWithAGD, LogisticRegressionWithSGD,
                               LinearRegressionWithSGD, SVMWithSGD,
                               SoftmaxRegressionWithAGD, LinearModel,
-                              MultinomialModel, regularization_path)
+                              MultinomialModel, OneVsRestWithAGD,
+                              OneVsRestModel, regularization_path)
 from .optimizer import (AcceleratedGradientDescent, GradientDescent, run,
                         run_mini_batch, runMiniBatch)
 from .gram import GramOperator, run_gram
@@ -79,6 +80,8 @@ __all__ = [
     "SoftmaxRegressionWithAGD",
     "LinearModel",
     "MultinomialModel",
+    "OneVsRestWithAGD",
+    "OneVsRestModel",
     "regularization_path",
     "evaluation",
     "HostStreamedDenseShard",

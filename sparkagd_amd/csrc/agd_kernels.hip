@@ -33,8 +33,9 @@
 //    taking raw device pointers and a hipStream_t, loaded via ctypes.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -fPIC -c agd_kernels.hip, then linked
-// with agd_multi_packed.o (the packed multi-column MFMA kernels) into
-// libagd_hip.so; see __graft_entry__.build().
+// with agd_multi_packed.o (the packed multi-column MFMA kernels) and
+// agd_tasks_ovr.o (the one-vs-rest task multipliers) into libagd_hip.so; see
+// __graft_entry__.build().
 
 #include <hip/hip_runtime.h>
 #include <hipblaslt/hipblaslt.h>
@@ -66,24 +67,16 @@ extern "C" const char* agd_last_error() { return g_err; }
 // Common device helpers
 // ---------------------------------------------------------------------------
 
-#define WAVE 64
-#define BLOCK 256
-#define WAVES_PER_BLOCK (BLOCK / WAVE)
+// WAVE / BLOCK / WAVES_PER_BLOCK, ll, wave_reduce_sum, the binary losses
+// (loss_mult) and the per-group evaluation of the task multipliers
+#include "agd_tasks.h"
 
-typedef long long ll;
 typedef unsigned short ubf16;  // raw bf16 bits
 
 __device__ __forceinline__ float bf2f(ubf16 u) {
   union { unsigned int i; float f; } v;
   v.i = ((unsigned int)u) << 16;
   return v.f;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_reduce_sum(T v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-  return v;
 }
 
 __device__ __forceinline__ float wave_reduce_max(float v) {
@@ -623,62 +616,8 @@ __global__ __launch_bounds__(BLOCK) void k_slab_reduce(TACC* __restrict__ part,
 // ---------------------------------------------------------------------------
 // K1b: elementwise multiplier + loss/count reduction
 //
-// loss conventions (z = <w, x_i>; identical algebra to MLlib 1.3's
-// LogisticGradient/LeastSquaresGradient/HingeGradient with margin = -z):
-//   logistic: m = sigmoid(z) - y ; loss = y>0 ? softplus(-z) : softplus(z)
-//   lsq:      m = 2(z-y)         ; loss = (z-y)^2
-//   hinge:    s = 2y-1 ; m = (s z < 1) ? -s : 0 ; loss = max(0, 1-s z)
+// The loss conventions and loss_mult are in agd_tasks.h.
 // ---------------------------------------------------------------------------
-
-#define LOSS_LOGISTIC 0
-#define LOSS_LSQ 1
-#define LOSS_HINGE 2
-#define LOSS_SMOOTH_HINGE 3  // quadratically smoothed (Rennie) hinge
-
-template <typename TACC>
-__device__ __forceinline__ TACC softplus(TACC t) {
-  // log(1 + e^t), overflow-stable
-  if (t > (TACC)0) return t + log1p(exp(-t));
-  return log1p(exp(t));
-}
-template <>
-__device__ __forceinline__ float softplus<float>(float t) {
-  if (t > 0.f) return t + log1pf(__expf(-t));
-  return log1pf(__expf(t));
-}
-
-// Per-example multiplier + loss for the binary losses (shared by the
-// margins-array and affine-combination kernels below).
-template <typename TACC>
-__device__ __forceinline__ void loss_mult(int loss_type, TACC z, TACC y,
-                                          TACC& m, TACC& l) {
-  if (loss_type == LOSS_LOGISTIC) {
-    m = (TACC)1 / ((TACC)1 + exp(-z)) - y;
-    l = (y > (TACC)0) ? softplus<TACC>(-z) : softplus<TACC>(z);
-  } else if (loss_type == LOSS_LSQ) {
-    const TACC diff = z - y;
-    m = (TACC)2 * diff;
-    l = diff * diff;
-  } else if (loss_type == LOSS_HINGE) {
-    const TACC s = (TACC)2 * y - (TACC)1;
-    const TACC sz = s * z;
-    m = (sz < (TACC)1) ? -s : (TACC)0;
-    l = (sz < (TACC)1) ? (TACC)1 - sz : (TACC)0;
-  } else {  // LOSS_SMOOTH_HINGE: 0 if sz>=1; (1-sz)^2/2 if 0<sz<1; 0.5-sz else
-    const TACC s = (TACC)2 * y - (TACC)1;
-    const TACC sz = s * z;
-    if (sz >= (TACC)1) {
-      m = (TACC)0;
-      l = (TACC)0;
-    } else if (sz > (TACC)0) {
-      m = -s * ((TACC)1 - sz);
-      l = (TACC)0.5 * ((TACC)1 - sz) * ((TACC)1 - sz);
-    } else {
-      m = -s;
-      l = (TACC)0.5 - sz;
-    }
-  }
-}
 
 template <typename TACC>
 __global__ __launch_bounds__(BLOCK) void k_multiplier(
@@ -4145,44 +4084,13 @@ extern "C" int agd_csr_grad_from_mult(
 // per-column training set and the prox with a per-column lambda.
 // ---------------------------------------------------------------------------
 
-// Grid cap of the task multiplier: each block leaves KC + 1 f64 partials, so
-// the workspace is TASKS_MAX_GRID * (KC + 1) doubles (sized by the wrapper
-// through agd_tasks_ws_doubles) and the one-block finish reads all of it.
-#define TASKS_MAX_GRID 1024
-
-static inline int tasks_grid(ll work_items, ll per_block) {
-  ll g = (work_items + per_block - 1) / per_block;
-  if (g > TASKS_MAX_GRID) g = TASKS_MAX_GRID;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 extern "C" long long agd_tasks_ws_doubles(int kc) {
   return (long long)TASKS_MAX_GRID * ((long long)kc + 1);
 }
 
-// One 4-column group of one row: a_ir from the fold test, the binary
-// loss_mult per live column, M scaled by s_i * scale_r, the unscaled
-// weighted loss into the caller's f64 partials.
-__device__ __forceinline__ void tasks_group(
-    const float* __restrict__ zp, float y, float s, int f, int loss_type,
-    int invert, const int (&h)[4], const float (&sc)[4], const bool (&live)[4],
-    float* __restrict__ mp, double (&ls)[4]) {
-  using f32x4 = __attribute__((ext_vector_type(4))) float;
-  const f32x4 zv = *(const f32x4*)zp;
-  f32x4 mv = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const bool train = (f != h[j]);
-    if (live[j] && (train != (invert != 0))) {
-      float m, l;
-      loss_mult<float>(loss_type, zv[j], y, m, l);
-      mv[j] = m * s * sc[j];
-      ls[j] += (double)l * (double)s;
-    }
-  }
-  if (mp) *(f32x4*)mp = mv;
-}
+// The per-group evaluation is agd_tasks.h's tasks_group, shared with the
+// one-vs-rest kernels of agd_tasks_ovr.hip; here every column sees the row's
+// own binary label (OVR = false: the target argument is not read).
 
 // KC in {4, 8, 16, 32}: elementwise over the n*KC/4 column groups with 16-B
 // accesses. The grid stride (gridDim*BLOCK groups) is a multiple of KC/4, so
@@ -4227,8 +4135,8 @@ __global__ __launch_bounds__(BLOCK) void k_multiplier_tasks(
     // no fold vector: no row is in any fold (never equals a holdout, -1 too)
     const int f = fold_id ? fold_id[i] : -2;
     if (c0 == 0) cnt += (double)s;
-    tasks_group(Z + g * 4, labels[i], s, f, loss_type, invert, h, sc, live,
-                mp, ls);
+    tasks_group<false>(Z + g * 4, labels[i], s, f, loss_type, invert, h, sc,
+                       live, h, mp, ls);
   }
   __shared__ double lds[WAVES_PER_BLOCK][KC];
   __shared__ double ldc[WAVES_PER_BLOCK];
@@ -4262,7 +4170,6 @@ __global__ __launch_bounds__(BLOCK) void k_multiplier_tasks(
 // column group at chunk + 4l; the column axis is walked in chunks of 256 so
 // the per-lane partials stay 4 f64 for any KC. Waves of a block hold the
 // same columns lane for lane, so the block stage is a 4-term LDS sum.
-#define TASKS_CHUNK (WAVE * 4)
 __global__ __launch_bounds__(BLOCK) void k_multiplier_tasks_anyk(
     const float* __restrict__ Z, const float* __restrict__ labels,
     const unsigned char* __restrict__ mask,
@@ -4302,8 +4209,8 @@ __global__ __launch_bounds__(BLOCK) void k_multiplier_tasks_anyk(
       const int f = fold_id ? fold_id[i] : -2;
       if (chunk == 0 && lane == 0) cnt += (double)s;
       if (active)
-        tasks_group(Z + i * KC + c0, labels[i], s, f, loss_type, invert, h,
-                    sc, live, mp, ls);
+        tasks_group<false>(Z + i * KC + c0, labels[i], s, f, loss_type, invert,
+                           h, sc, live, h, mp, ls);
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) lds[wid][lane * 4 + j] = ls[j];
@@ -4368,6 +4275,21 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_task_partials(
   block_reduce_partial<1>(acc, loss_count + 1);  // blockIdx.x == 0
 }
 
+// Host helper shared with agd_tasks_ovr.hip: the finish over the `grid`
+// block partials a task multiplier left in ws.
+extern "C" int agd_tasks_finish(void* ws, int grid, int kc, int R,
+                                const void* task_scale, void* task_loss,
+                                void* loss_count, void* stream) {
+  double* part = (double*)ws;
+  hipLaunchKernelGGL(k_reduce_task_partials, dim3(1), dim3(BLOCK), 0,
+                     (hipStream_t)stream, part,
+                     part + (ll)TASKS_MAX_GRID * kc, grid, kc, R,
+                     (const float*)task_scale, (double*)task_loss,
+                     (double*)loss_count);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
 // M may be null (loss-only call). task_loss f64[R] and loss_count f64[2] are
 // overwritten. ws holds agd_tasks_ws_doubles(kc) doubles.
 extern "C" int agd_multiplier_tasks(
@@ -4414,11 +4336,8 @@ extern "C" int agd_multiplier_tasks(
       break;
   }
 #undef LAUNCH_MT
-  hipLaunchKernelGGL(k_reduce_task_partials, dim3(1), dim3(BLOCK), 0, s, part,
-                     cnt_part, grid, kc, R, (const float*)task_scale,
-                     (double*)task_loss, (double*)loss_count);
-  HIP_CHECK(hipGetLastError());
-  return 0;
+  return agd_tasks_finish(ws, grid, kc, R, task_scale, task_loss, loss_count,
+                          stream);
 }
 
 // k_prox with a per-task lambda: w is the flat feature-major [d, R] block, so

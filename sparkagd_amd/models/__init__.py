@@ -14,7 +14,7 @@ from .updater import Updater, SimpleUpdater, L1Updater, SquaredL2Updater, Elasti
 from .trainers import (LogisticRegressionWithAGD, LinearRegressionWithAGD, SVMWithAGD,
                        LogisticRegressionWithSGD, LinearRegressionWithSGD, SVMWithSGD,
                        SoftmaxRegressionWithAGD, LinearModel, MultinomialModel,
-                       regularization_path)
+                       OneVsRestWithAGD, OneVsRestModel, regularization_path)
 
 __all__ = [
     "Gradient",
@@ -37,5 +37,7 @@ __all__ = [
     "SoftmaxRegressionWithAGD",
     "LinearModel",
     "MultinomialModel",
+    "OneVsRestWithAGD",
+    "OneVsRestModel",
     "regularization_path",
 ]

@@ -42,6 +42,13 @@ class MultiTaskGradient(Gradient):
     ``sample_weight`` must be the shard's ``sample_weight`` when it has one:
     the fold totals N_r are weighted sums. Dense and CSR shards only; direct
     solver only.
+
+    One-vs-rest: with ``target_class`` (a class id >= 0 per task) the shard's
+    labels are class indices and task r is the binary problem "class
+    ``target_class[r]`` against the rest", ``y_ir = [label_i ==
+    target_class[r]]``. Without ``fold_id`` every scale is 1 and the objective
+    is the sum of the R mean losses and regularisers, whose minimiser is the
+    stack of the R one-vs-rest minimisers.
     """
 
     IS_MULTICLASS = True  # [n, KC] margins, shard left raw by the pack policy
@@ -50,7 +57,8 @@ class MultiTaskGradient(Gradient):
     def __init__(self, base: Gradient, num_tasks: int,
                  fold_id: Optional[torch.Tensor] = None,
                  holdout: Optional[Sequence[int]] = None, comm=None,
-                 sample_weight: Optional[torch.Tensor] = None):
+                 sample_weight: Optional[torch.Tensor] = None,
+                 target_class: Optional[Sequence[int]] = None):
         if getattr(base, "IS_MULTICLASS", False) or getattr(base, "LOSS_TYPE", -1) < 0:
             raise ValueError("base must be one of the binary gradients")
         if num_tasks < 1:
@@ -61,6 +69,15 @@ class MultiTaskGradient(Gradient):
         self.num_classes = self.num_tasks
         self.fold_id = None
         self.holdout = None
+        self.target_class = None
+        if target_class is not None:
+            t = torch.as_tensor(list(target_class)).reshape(-1).cpu()
+            if t.numel() != self.num_tasks:
+                raise ValueError("target_class must have one entry per task")
+            if (t.dtype.is_floating_point or t.dtype == torch.bool
+                    or bool((t < 0).any())):
+                raise ValueError("target_class entries are class ids >= 0")
+            self.target_class = t.to(torch.int32)
         self._weighted = sample_weight is not None
         if holdout is not None:
             h = torch.as_tensor(holdout, dtype=torch.int64).reshape(-1).cpu()
@@ -140,7 +157,8 @@ class MultiTaskGradient(Gradient):
                 "the fold totals N_r are weighted sums")
 
     def _on(self, device):
-        """(fold_id, holdout, task_scale) placed on ``device`` (cached)."""
+        """(fold_id, holdout, task_scale, target_class) placed on ``device``
+        (cached)."""
         t = self._dev_cache.get(device)
         if t is None:
             scale = self.task_scale.to(
@@ -148,7 +166,9 @@ class MultiTaskGradient(Gradient):
                 dtype=torch.float32 if device.type == "cuda" else torch.float64)
             t = (None if self.fold_id is None else self.fold_id.to(device),
                  None if self.holdout is None else self.holdout.to(device),
-                 scale)
+                 scale,
+                 None if self.target_class is None
+                 else self.target_class.to(device))
             self._dev_cache[device] = t
         return t
 
@@ -174,20 +194,21 @@ class MultiTaskGradient(Gradient):
         padded margins — the loss-only multiplier call; ``invert=True`` sums
         each task's HELD-OUT rows instead of its training rows."""
         self._check_shard(shard)
-        fold, hold, scale = self._on(margins.device)
+        fold, hold, scale, target = self._on(margins.device)
         _, task_loss, lc = mt.multiplier_tasks(
             margins, shard.labels, self.LOSS_TYPE, self.num_tasks, scale, mask,
-            shard.sample_weight, fold, hold, invert, need_mult=False)
+            shard.sample_weight, fold, hold, invert, need_mult=False,
+            target=target)
         return task_loss, lc
 
     def multiplier_loss(self, shard, margins, mask=None):
         """(padded multiplier flat [n*KC], loss_count) from padded margins —
         the n-space stage (zero data passes)."""
         self._check_shard(shard)
-        fold, hold, scale = self._on(margins.device)
+        fold, hold, scale, target = self._on(margins.device)
         m, task_loss, lc = mt.multiplier_tasks(
             margins, shard.labels, self.LOSS_TYPE, self.num_tasks, scale, mask,
-            shard.sample_weight, fold, hold)
+            shard.sample_weight, fold, hold, target=target)
         self.last_task_loss = task_loss
         return m, lc
 

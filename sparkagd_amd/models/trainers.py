@@ -10,6 +10,7 @@ with ``predict``.
 
 from __future__ import annotations
 
+import dataclasses
 from typing import Optional, Union
 
 import torch
@@ -17,7 +18,8 @@ import torch
 from ..config import AGDConfig
 from ..optimizer import AcceleratedGradientDescent
 from ..parallel.comm import Communicator
-from .gradient import HingeGradient, LeastSquaresGradient, LogisticGradient
+from .gradient import (HingeGradient, LeastSquaresGradient, LogisticGradient,
+                       SmoothedHingeGradient)
 from .updater import SimpleUpdater, SquaredL2Updater, Updater
 
 
@@ -452,6 +454,153 @@ class SoftmaxRegressionWithAGD:
         if scaler is not None:
             w = scaler.unscale_weights(w, num_classes)
         return MultinomialModel(w, opt.loss_history, num_classes)
+
+
+class OneVsRestModel:
+    """K one-vs-rest binary models over the same features: weights [d, K],
+    column c scoring "class c against the rest". ``predict`` is the argmax of
+    the margins, the lowest class index winning ties."""
+
+    def __init__(self, weights: torch.Tensor, loss_history, num_classes: int,
+                 link: str):
+        self.weights = weights.reshape(-1, int(num_classes))
+        self.loss_history = list(loss_history)
+        self.num_classes = int(num_classes)
+        self.link = link
+
+    def score(self, shard) -> torch.Tensor:
+        """Margins [n, K] of a whole dense or CSR shard through the
+        multi-column margins pass (scoring route: f32 weights are kept on a
+        bf16 shard); the features are read in place."""
+        from ..ops.multiclass import multi_margins, padded_k
+
+        k = self.num_classes
+        w = _weights_for(shard, self.weights.reshape(-1))
+        zp = multi_margins(shard, w, k, scoring=True)
+        return zp.reshape(shard.n, padded_k(k))[:, :k]
+
+    def predict(self, shard) -> torch.Tensor:
+        """Class indices (f32) of a shard's rows."""
+        z = self.score(shard)
+        # argmax leaves the choice among equal maxima open: take the first
+        first = (z == z.max(dim=1, keepdim=True).values).to(torch.uint8)
+        return first.argmax(dim=1).to(torch.float32)
+
+    def save(self, path: str) -> None:
+        _save_model(path, self.weights,
+                    {"kind": "one_vs_rest", "num_classes": self.num_classes,
+                     "link": self.link, "loss_history": self.loss_history})
+
+    @classmethod
+    def load(cls, path: str, device=None) -> "OneVsRestModel":
+        w, meta = _load_model(path, device)
+        if meta.get("kind") != "one_vs_rest":
+            raise ValueError(f"not a OneVsRestModel checkpoint: {meta.get('kind')}")
+        return cls(w, meta.get("loss_history", []), meta["num_classes"],
+                   meta["link"])
+
+
+def _check_class_labels(data, num_classes: int, comm: Communicator) -> None:
+    """Labels of ``data`` are integers in [0, num_classes), else ValueError
+    (one pass over the labels; the ranks of a sharded run agree)."""
+    y = data.labels
+    bad = ((y != y.round()) | (y < 0) | (y >= num_classes)).any()
+    flag = torch.tensor([float(bad)], dtype=torch.float64)
+    comm.allreduce_(flag, op="max")
+    if bool(flag[0] > 0):
+        raise ValueError(
+            f"labels must be class indices: integers in [0, {num_classes})")
+
+
+class OneVsRestWithAGD:
+    """One-vs-rest multiclass trainer: K binary models ("class c against the
+    rest") with a logistic, smoothed-hinge (SVM) or squared loss, trained as
+    the K columns of one weight block, so every stream of the shard serves
+    all K (``MultiTaskGradient`` with a target class per column)."""
+
+    # the hinge is the quadratically smoothed one: AGD assumes a Lipschitz
+    # gradient
+    LOSSES = {"logistic": (LogisticGradient, "logistic"),
+              "hinge": (SmoothedHingeGradient, "hinge"),
+              "squared": (LeastSquaresGradient, "identity")}
+
+    @classmethod
+    def train(
+        cls,
+        data,
+        num_classes: int,
+        loss: str = "logistic",
+        num_iterations: int = 100,
+        reg_param=0.0,
+        convergence_tol: float = 1e-4,
+        updater: Optional[Updater] = None,
+        initial_weights: Optional[torch.Tensor] = None,
+        comm: Optional[Communicator] = None,
+        config: Optional[AGDConfig] = None,
+        pack: bool = False,
+    ) -> OneVsRestModel:
+        """``data`` is a dense (f32, bf16, fp8, packed) or CSR shard whose
+        labels are class indices in [0, num_classes); a shard per rank with
+        ``comm``. ``reg_param`` is one strength, or one per class (then a
+        squared-L2 or simple ``updater`` still tracks its margins where
+        ``MultiTaskGradient.rounds_margin_weights`` allows).
+        ``initial_weights`` is the flat [d * num_classes] block. ``pack=True``
+        packs a dense GPU shard first, as in ``SoftmaxRegressionWithAGD``."""
+        from ..optimizer import run
+        from .multitask import MultiTaskGradient, PerTaskUpdater
+
+        if loss not in cls.LOSSES:
+            raise ValueError(f"loss must be one of {sorted(cls.LOSSES)}")
+        k = int(num_classes)
+        if k < 2:
+            raise ValueError("num_classes must be >= 2")
+        if getattr(data, "kind", None) not in ("dense", "csr"):
+            raise ValueError(
+                "OneVsRestWithAGD trains on dense and CSR shards only; got "
+                f"{type(data).__name__}")
+        lams = torch.as_tensor(reg_param, dtype=torch.float64).reshape(-1)
+        if lams.numel() not in (1, k):
+            raise ValueError(
+                f"reg_param must be a scalar or one value per class ({k})")
+        if bool((lams < 0).any()) or not bool(torch.isfinite(lams).all()):
+            raise ValueError("reg_param must be finite and >= 0")
+        comm = comm or Communicator()
+        _check_class_labels(data, k, comm)
+        if pack and data.kind == "dense" and data.features.is_cuda:
+            data.pack()
+
+        cfg = dataclasses.replace(config) if config is not None else AGDConfig()
+        cfg.num_iterations = num_iterations
+        cfg.convergence_tol = convergence_tol
+        cfg.validate()
+        if cfg.solver == "gram":
+            raise ValueError("OneVsRestWithAGD runs on the direct solver only "
+                             "(config.solver='gram' is not supported)")
+        if updater is None:
+            updater = SquaredL2Updater() if bool((lams > 0).any()) else SimpleUpdater()
+        if lams.numel() == 1 or len(set(lams.tolist())) == 1:
+            run_updater, run_reg = updater, float(lams[0])
+        else:
+            run_updater, run_reg = PerTaskUpdater(updater, lams.tolist()), 1.0
+        grad_cls, link = cls.LOSSES[loss]
+        grad = MultiTaskGradient(grad_cls(), k, comm=comm,
+                                 sample_weight=data.sample_weight,
+                                 target_class=range(k))
+        if initial_weights is None:
+            wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
+            initial_weights = torch.zeros(data.d * k, device=data.device,
+                                          dtype=wdtype)
+        elif initial_weights.numel() != data.d * k:
+            raise ValueError(f"initial_weights must hold [{data.d}, {k}]")
+        w, hist = run(
+            data, grad, run_updater, cfg.convergence_tol, cfg.num_iterations,
+            run_reg, initial_weights.reshape(-1), cfg.L0, cfg.Lexact, cfg.beta,
+            cfg.alpha, cfg.may_restart,
+            loss_history_mode=cfg.loss_history_mode, comm=comm,
+            track_margins=cfg.track_margins,
+            margin_refresh_every=cfg.margin_refresh_every,
+            backtrack_tol=cfg.backtrack_tol)
+        return OneVsRestModel(w, hist, k, link)
 
 
 class _SGDTrainer:

@@ -167,6 +167,9 @@ def load() -> ctypes.CDLL:
     lib.agd_multiplier_tasks.restype = I
     lib.agd_multiplier_tasks.argtypes = [P, P, P, P, P, P, P, I, I, LL, I, I,
                                          P, P, P, P, P]
+    lib.agd_multiplier_tasks_ovr.restype = I
+    lib.agd_multiplier_tasks_ovr.argtypes = [P, P, P, P, P, P, P, P, I, I, LL,
+                                             I, I, P, P, P, P, P]
     lib.agd_prox_tasks.restype = I
     lib.agd_prox_tasks.argtypes = [I, P, P, D, P, P, I, P, P, LL, I, P, P]
     lib.agd_at_margin_update_tasks.restype = I
@@ -806,9 +809,13 @@ def multiplier_tasks(
     holdout: Optional[torch.Tensor] = None,
     invert: bool = False,
     need_mult: bool = True,
+    target: Optional[torch.Tensor] = None,
 ) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
     """(M [n*kc] f32 or None, task_loss f64[r], loss_count f64[2]) from padded
-    margins of ``r`` binary tasks — the n-space stage of MultiTaskGradient."""
+    margins of ``r`` binary tasks — the n-space stage of MultiTaskGradient.
+    With ``target`` (a class id per task) ``labels`` are class indices and
+    task t sees the label ``[labels == target[t]]`` (the one-vs-rest
+    kernels)."""
     lib = load()
     dev = margins_padded_flat.device
     if margins_padded_flat.dtype != torch.float32:
@@ -834,12 +841,18 @@ def multiplier_tasks(
          if need_mult else None)
     task_loss = torch.empty(r, dtype=torch.float64, device=dev)
     loss_count = torch.empty(2, dtype=torch.float64, device=dev)
-    rc = lib.agd_multiplier_tasks(
-        _ptr(margins_padded_flat.contiguous()), _ptr(labels), _ptr(mask),
-        _ptr(sw), _ptr(fold_id), _ptr(holdout), _ptr(task_scale),
-        int(loss_type), int(bool(invert)), n, r, kc, _ptr(M), _ptr(task_loss),
-        _ptr(loss_count), _ptr(_tasks_ws(dev, kc)),
-        _stream(margins_padded_flat))
+    head = (_ptr(margins_padded_flat.contiguous()), _ptr(labels), _ptr(mask),
+            _ptr(sw), _ptr(fold_id), _ptr(holdout), _ptr(task_scale))
+    tail = (int(loss_type), int(bool(invert)), n, r, kc, _ptr(M),
+            _ptr(task_loss), _ptr(loss_count), _ptr(_tasks_ws(dev, kc)),
+            _stream(margins_padded_flat))
+    if target is None:
+        rc = lib.agd_multiplier_tasks(*head, *tail)
+    else:
+        target = target.to(device=dev, dtype=torch.int32).contiguous()
+        if target.numel() != r:
+            raise ValueError("target must be [num_tasks]")
+        rc = lib.agd_multiplier_tasks_ovr(*head, _ptr(target), *tail)
     _check(rc)
     return M, task_loss, loss_count
 

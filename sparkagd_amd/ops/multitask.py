@@ -19,6 +19,10 @@ lives here:
   its own mean;
 * the prox with a per-column lambda.
 
+One-vs-rest multiclass is the same stack with a target class per column:
+``target`` [R] turns the shard's class-index labels into the binary label
+``y_ir = [label_i == target[r]]`` inside the multiplier.
+
 Padding is that of ``multiclass.padded_k``; pad columns of M are exact zeros.
 """
 
@@ -44,6 +48,7 @@ def ref_multiplier_tasks(
     fold_id: Optional[torch.Tensor] = None,
     holdout: Optional[torch.Tensor] = None,
     invert: bool = False,
+    target: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """(M [n, R], task_loss f64 [R], loss_count f64 [2]) in z's dtype.
 
@@ -51,11 +56,20 @@ def ref_multiplier_tasks(
     holdout_r]``, the held-out rows); ``M = a · s · scale · m``;
     ``task_loss[r] = sum_i a_ir s_i l`` (unscaled); ``loss_count = (sum_r
     scale_r · task_loss[r], sum_i mask_i s_i)``. Without ``fold_id`` no row
-    is in any fold; without ``holdout`` every task has ``holdout = -1``."""
+    is in any fold; without ``holdout`` every task has ``holdout = -1``.
+
+    One-vs-rest: with ``target`` [R] (a class id per task) ``labels`` are
+    class indices and task r sees the binary label ``[labels_i ==
+    target[r]]`` (1 / 0, the convention of all four binary losses)."""
     n, r = z.shape
     acc = z.dtype
     dev = z.device
-    m, loss = _ref._multiplier_and_loss(z, labels.reshape(n, 1), loss_type)
+    if target is None:
+        y = labels.reshape(n, 1)
+    else:
+        y = (labels.long()[:, None]
+             == target.to(device=labels.device, dtype=torch.int64)[None, :])
+    m, loss = _ref._multiplier_and_loss(z, y, loss_type)
     row = torch.ones(n, dtype=acc, device=dev)
     if mask is not None:
         row = row * mask.to(acc)
@@ -154,20 +168,24 @@ def multiplier_tasks(
     holdout: Optional[torch.Tensor] = None,
     invert: bool = False,
     need_mult: bool = True,
+    target: Optional[torch.Tensor] = None,
 ) -> Tuple[Optional[torch.Tensor], torch.Tensor, torch.Tensor]:
     """(M padded flat [n*KC] or None, task_loss f64 [R], loss_count f64 [2])
     from padded margins [n*KC] — zero data passes. ``need_mult=False`` is the
-    loss-only call (no M is written)."""
+    loss-only call (no M is written). ``target`` [R]: one-vs-rest, task r
+    against the label ``[labels == target[r]]``."""
     kc = padded_k(num_tasks)
+    if target is not None and target.numel() != num_tasks:
+        raise ValueError("target must be [num_tasks]")
     if _use_hip(margins_padded_flat):
         return hiplib.multiplier_tasks(
             margins_padded_flat, labels, loss_type, num_tasks, kc, task_scale,
-            mask, sample_weight, fold_id, holdout, invert, need_mult)
+            mask, sample_weight, fold_id, holdout, invert, need_mult, target)
     n = margins_padded_flat.numel() // kc
     z = margins_padded_flat.reshape(n, kc)[:, :num_tasks]
     m, task_loss, lc = ref_multiplier_tasks(
         z, labels, loss_type, task_scale, mask, sample_weight, fold_id,
-        holdout, invert)
+        holdout, invert, target)
     if not need_mult:
         return None, task_loss, lc
     return _pad_classes(m, kc).reshape(-1), task_loss, lc
