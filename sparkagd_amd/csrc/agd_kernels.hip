@@ -116,7 +116,9 @@ __device__ __forceinline__ void block_reduce_partial(double (&acc)[NACC],
 
 // Final stage: one block sums the per-block partials into out[NACC]
 // (ACCUMULATES into out so callers may chain; callers zero out first).
-template <int NACC>
+// SET overwrites out instead: nothing to zero, for slots of a scalar block
+// that lives across calls (agd_at_step_tail).
+template <int NACC, bool SET = false>
 __global__ __launch_bounds__(BLOCK) void k_reduce_partials(
     const double* __restrict__ part, int nblocks, double* __restrict__ out) {
   double acc[NACC];
@@ -141,7 +143,7 @@ __global__ __launch_bounds__(BLOCK) void k_reduce_partials(
 #pragma unroll
       for (int off = WAVES_PER_BLOCK / 2; off > 0; off >>= 1)
         v += __shfl_xor(v, off, WAVE);
-      if (lane == 0) out[k] += v;
+      if (lane == 0) out[k] = SET ? v : out[k] + v;
     }
   }
 }
@@ -1695,6 +1697,97 @@ __global__ __launch_bounds__(BLOCK) void k_fused_scalars(
   block_reduce_partial<5>(acc, out_part);
 }
 
+// One element of the fused step tail (k_at_step_tail), every rounding
+// written out so that it is the rounding of the kernel sequence it replaces.
+// Left to contraction the same spellings fuse differently from kernel to
+// kernel, and inside one kernel between the vector body and the tail:
+//   k_prox      z = fma(1 - ts*tl [one fma], zo, -(ts*g))  (L2)
+//               z = fma(-ts, g, zo)                          (simple)
+//   k_axpby     x = fma(1-th, xo, th*z); the f32 scalar tail alone rounds
+//               both products and adds them (F32_TAIL)
+//   k_fused_scalars, and k_prox(x, 0, step 0) for the value of the
+//               regulariser at x: one fma per f64 accumulator and element
+// c = fma(-ts, tl, 1) and hl = 0.5 * (double)tl are formed by the caller.
+template <typename T, bool F32_TAIL>
+__device__ __forceinline__ void step_tail_elem(int kind, T ts, T c, T tom,
+                                               T tth, double hl, T xo, T zo,
+                                               T yi, T gi, T& zn, T& xn,
+                                               double (&a)[6]) {
+#pragma clang fp contract(off)
+  if (kind == PROX_L2) {
+    const T sg = ts * gi;
+    zn = fma(c, zo, -sg);
+  } else {
+    zn = fma(-ts, gi, zo);
+  }
+  const T thz = tth * zn;
+  if (F32_TAIL) {
+    const T omx = tom * xo;
+    xn = omx + thz;
+  } else {
+    xn = fma(tom, xo, thz);
+  }
+  const double xd = (double)xn, gd = (double)gi;
+  const double xy = xd - (double)yi, dx = xd - (double)xo;
+  a[0] = fma(xy, xy, a[0]);
+  a[1] = fma(xy, gd, a[1]);
+  a[2] = fma(xd, xd, a[2]);
+  a[3] = fma(dx, dx, a[3]);
+  a[4] = fma(gd, dx, a[4]);
+  if (kind == PROX_L2) {
+    const double hx = hl * xd;
+    a[5] = fma(hx, xd, a[5]);
+  }
+}
+
+// Fused tail of one AGD trial for the affine prox kinds (simple, squared
+// L2): ONE pass over (x_old, z_old, y, g_y) instead of k_prox + k_axpby +
+// k_fused_scalars + the k_prox(x, 0, 0) behind reg_value, producing
+//   z = prox(z_old, g_y, step)        x = (1-theta)*x_old + theta*z
+//   part[.][0..4] = the five k_fused_scalars sums of (x, y, g_y, x_old)
+//   part[.][5]    = the regulariser's value at x (0 for the simple kind)
+// bit for bit what those kernels give: the same grid and per-thread element
+// order (16-B body, scalar tail), the same block_reduce tree per sum, the
+// roundings of step_tail_elem. Finished by k_reduce_partials<6, true>, which
+// overwrites its six slots.
+template <typename T>
+__global__ __launch_bounds__(BLOCK) void k_at_step_tail(
+    int kind, const T* __restrict__ x_old, const T* __restrict__ z_old,
+    const T* __restrict__ y, const T* __restrict__ gy, double theta,
+    double step, double lam, T* __restrict__ z, T* __restrict__ x,
+    double* __restrict__ part, ll n) {
+  constexpr int VE = 16 / sizeof(T);
+  const ll stride = (ll)gridDim.x * BLOCK;
+  const ll gid = (ll)blockIdx.x * BLOCK + threadIdx.x;
+  const T ts = (T)step, tl = (T)lam, tth = (T)theta, tom = (T)(1.0 - theta);
+  const T c = fma(-ts, tl, (T)1);
+  const double hl = 0.5 * (double)tl;
+  double acc[6] = {0, 0, 0, 0, 0, 0};
+  const ll nv = n / VE;
+  for (ll i = gid; i < nv; i += stride) {
+    T xo[VE], zo[VE], yv[VE], gv[VE], zn[VE], xn[VE];
+    loadAcc<T, VE>(x_old + i * VE, xo);
+    loadAcc<T, VE>(z_old + i * VE, zo);
+    loadAcc<T, VE>(y + i * VE, yv);
+    loadAcc<T, VE>(gy + i * VE, gv);
+#pragma unroll
+    for (int k = 0; k < VE; ++k)
+      step_tail_elem<T, false>(kind, ts, c, tom, tth, hl, xo[k], zo[k], yv[k],
+                               gv[k], zn[k], xn[k], acc);
+    storeAcc<T, VE>(z + i * VE, zn);
+    storeAcc<T, VE>(x + i * VE, xn);
+  }
+  const ll t = nv * VE + gid;  // tail (< VE elements)
+  if (t < n) {
+    T zn, xn;
+    step_tail_elem<T, sizeof(T) == 4>(kind, ts, c, tom, tth, hl, x_old[t],
+                                      z_old[t], y[t], gy[t], zn, xn, acc);
+    z[t] = zn;
+    x[t] = xn;
+  }
+  block_reduce_partial<6>(acc, part);
+}
+
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_dot_diff(
     const T* __restrict__ x, const T* __restrict__ y, const T* __restrict__ gx,
@@ -3243,6 +3336,43 @@ extern "C" int agd_fused_scalars(const void* x, const void* y, const void* gy,
   }
   hipLaunchKernelGGL((k_reduce_partials<5>), dim3(1), dim3(BLOCK), 0, s,
                      (double*)red_ws, grid, (double*)out);
+  HIP_CHECK(hipGetLastError());
+  return 0;
+}
+
+// scal (double[6]) is overwritten: the five fused scalars, then the
+// regulariser's value at x. Simple and squared-L2 prox only; z and x must not
+// alias an input; red_ws holds 6 doubles per block of the grid.
+extern "C" int agd_at_step_tail(int kind, const void* x_old, const void* z_old,
+                                const void* y, const void* gy, double theta,
+                                double step, double lam, void* z, void* x,
+                                void* scal, long long n, int dtype,
+                                void* red_ws, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if ((kind != PROX_SIMPLE && kind != PROX_L2) || n < 1 || !x_old || !z_old ||
+      !y || !gy || !z || !x || !scal || !red_ws) {
+    snprintf(g_err, sizeof(g_err),
+             "agd_at_step_tail: bad kind %d / n %lld or a null pointer", kind,
+             n);
+    return 2;
+  }
+  const int grid = grid_for(n, BLOCK * 4);
+  if (dtype == 1)
+    hipLaunchKernelGGL((k_at_step_tail<float>), dim3(grid), dim3(BLOCK), 0, s,
+                       kind, (const float*)x_old, (const float*)z_old,
+                       (const float*)y, (const float*)gy, theta, step, lam,
+                       (float*)z, (float*)x, (double*)red_ws, (ll)n);
+  else if (dtype == 2)
+    hipLaunchKernelGGL((k_at_step_tail<double>), dim3(grid), dim3(BLOCK), 0, s,
+                       kind, (const double*)x_old, (const double*)z_old,
+                       (const double*)y, (const double*)gy, theta, step, lam,
+                       (double*)z, (double*)x, (double*)red_ws, (ll)n);
+  else {
+    snprintf(g_err, sizeof(g_err), "agd_at_step_tail: bad dtype %d", dtype);
+    return 2;
+  }
+  hipLaunchKernelGGL((k_reduce_partials<6, true>), dim3(1), dim3(BLOCK), 0, s,
+                     (double*)red_ws, grid, (double*)scal);
   HIP_CHECK(hipGetLastError());
   return 0;
 }

@@ -354,6 +354,24 @@ def fused_scalars(
     return reference.fused_scalars(x, y, g_y, x_old)
 
 
+def at_step_tail(kind: int, x_old: torch.Tensor, z_old: torch.Tensor,
+                 y: torch.Tensor, g_y: torch.Tensor, theta: float, step: float,
+                 lam: float, scal: torch.Tensor
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused tail of an AGD trial, simple and squared-L2 prox: returns
+    ``(z, x)`` with ``z = prox(z_old, g_y, step)`` and ``x = (1-theta)*x_old +
+    theta*z``, and overwrites ``scal`` (float64[6]) with the five
+    ``fused_scalars(x, y, g_y, x_old)`` and the regulariser's value at x —
+    bit for bit the results of ``prox``, ``axpby``, ``fused_scalars`` and
+    ``prox(x, 0, 0.0)`` in sequence (one kernel on GPU, that sequence on
+    CPU)."""
+    if _use_hip(x_old):
+        return _get_hip().at_step_tail(kind, x_old, z_old, y, g_y, theta, step,
+                                       lam, scal)
+    return reference.at_step_tail(kind, x_old, z_old, y, g_y, theta, step, lam,
+                                  scal)
+
+
 def dot_diff(
     x: torch.Tensor, y: torch.Tensor, g_x: torch.Tensor, g_y: torch.Tensor
 ) -> torch.Tensor:

@@ -102,6 +102,8 @@ def load() -> ctypes.CDLL:
     lib.agd_prox.argtypes = [I, P, P, D, D, D, P, P, LL, I, P, P]
     lib.agd_fused_scalars.restype = I
     lib.agd_fused_scalars.argtypes = [P, P, P, P, P, LL, I, P, P]
+    lib.agd_at_step_tail.restype = I
+    lib.agd_at_step_tail.argtypes = [I, P, P, P, P, D, D, D, P, P, P, LL, I, P, P]
     lib.agd_dot_diff.restype = I
     lib.agd_dot_diff.argtypes = [P, P, P, P, P, LL, I, P, P]
     lib.agd_gemm_bf16f32_nt.restype = I
@@ -200,10 +202,10 @@ _red_ws_cache = {}
 
 def _red_ws(device) -> torch.Tensor:
     """Per-device fp64 partials buffer for the two-stage scalar reductions
-    (max grid 8192 x up to 5 accumulators)."""
+    (max grid 8192 x up to 6 accumulators)."""
     t = _red_ws_cache.get(device)
     if t is None:
-        t = torch.empty(8192 * 5, dtype=torch.float64, device=device)
+        t = torch.empty(8192 * 6, dtype=torch.float64, device=device)
         _red_ws_cache[device] = t
     return t
 
@@ -1117,6 +1119,32 @@ def fused_scalars(x: torch.Tensor, y: torch.Tensor, g_y: torch.Tensor, x_old: to
                                _ptr(_red_ws(x.device)), _stream(x))
     _check(rc)
     return out
+
+
+def at_step_tail(kind: int, x_old: torch.Tensor, z_old: torch.Tensor,
+                 y: torch.Tensor, g_y: torch.Tensor, theta: float, step: float,
+                 lam: float, scal: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused tail of an AGD trial (k_at_step_tail): (z, x), and the six
+    scalars written over ``scal`` — a contiguous f64[6] view, typically a
+    slice of the run's scalar block. Nothing is zeroed and nothing allocated
+    but the two outputs."""
+    lib = load()
+    if scal.dtype != torch.float64 or scal.numel() != 6 \
+            or not scal.is_contiguous() or scal.device != x_old.device:
+        raise ValueError("scal must be a contiguous float64[6] on the vectors' device")
+    n = x_old.numel()
+    for t in (z_old, y, g_y):
+        if t.numel() != n or t.dtype != x_old.dtype:
+            raise ValueError("x_old, z_old, y and g_y must share length and dtype")
+    z = torch.empty_like(x_old, memory_format=torch.contiguous_format)
+    x = torch.empty_like(z)
+    rc = lib.agd_at_step_tail(
+        kind, _ptr(x_old.contiguous()), _ptr(z_old.contiguous()),
+        _ptr(y.contiguous()), _ptr(g_y.contiguous()), float(theta), float(step),
+        float(lam), _ptr(z), _ptr(x), _ptr(scal), n, _VEC_DTYPE[x_old.dtype],
+        _ptr(_red_ws(x_old.device)), _stream(x_old))
+    _check(rc)
+    return z, x
 
 
 def dot_diff(x: torch.Tensor, y: torch.Tensor, g_x: torch.Tensor, g_y: torch.Tensor) -> torch.Tensor:

@@ -319,6 +319,24 @@ def axpby(a: float, x: torch.Tensor, b: float, y: torch.Tensor, out: Optional[to
     return out
 
 
+def at_step_tail(kind: int, x_old: torch.Tensor, z_old: torch.Tensor,
+                 y: torch.Tensor, g_y: torch.Tensor, theta: float, step: float,
+                 lam: float, scal: torch.Tensor
+                 ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Tail of an AGD trial as the sequence of ops that the fused kernel
+    replaces: ``z = prox(z_old, g_y, step)``, ``x = (1-theta)*x_old +
+    theta*z``, then ``scal[0:5] = fused_scalars(x, y, g_y, x_old)`` and
+    ``scal[5]`` = the regulariser's value at x. ``scal`` (float64[6]) is
+    overwritten; returns ``(z, x)``."""
+    if kind not in (PROX_SIMPLE, PROX_SQUARED_L2):
+        raise ValueError("at_step_tail serves the simple and squared-L2 prox")
+    z, _ = prox(kind, z_old, g_y, step, lam)
+    x = axpby(1.0 - theta, x_old, theta, z)
+    scal[:5] = fused_scalars(x, y, g_y, x_old)
+    scal[5] = prox(kind, x, torch.zeros_like(x), 0.0, lam)[1]
+    return z, x
+
+
 def fused_scalars(
     x: torch.Tensor,
     y: torch.Tensor,

@@ -30,7 +30,7 @@ import torch
 from . import ops
 from .config import AGDConfig
 from .models.gradient import Gradient
-from .models.updater import Updater
+from .models.updater import SimpleUpdater, SquaredL2Updater, Updater
 from .parallel.comm import Communicator
 
 logger = logging.getLogger(__name__)
@@ -213,7 +213,7 @@ def run(
         apply_pack_policy(data, pack_dense, num_iterations - start_iter + 1,
                           gradient)
 
-    eval_state = {"n": 0, "seconds": 0.0}
+    eval_state = {"n": 0, "seconds": 0.0, "fetches": 0}
 
     def apply_smooth(v, mask=None, need_grad=True):
         t0 = time.perf_counter()
@@ -221,6 +221,7 @@ def run(
         # _apply_smooth ends with the host fetch of (loss, count), so this
         # wall segment covers the kernels + all-reduce for the evaluation.
         eval_state["n"] += 1
+        eval_state["fetches"] += 1
         eval_state["seconds"] += time.perf_counter() - t0
         return out
 
@@ -245,8 +246,14 @@ def run(
         if count > 0 and grad_sum is not None:
             grad_sum.div_(count)
         eval_state["n"] += 1
+        eval_state["fetches"] += 1
         eval_state["seconds"] += time.perf_counter() - t0
         return (loss_sum / count if count > 0 else float("nan")), grad_sum, count
+
+    def fetch(t):
+        """float of a device scalar: one host round trip."""
+        eval_state["fetches"] += 1
+        return float(t)
 
     # Margin-state tracking eligibility (see docstring).
     # A PerTaskUpdater over an affine base is affine per COLUMN of a
@@ -264,6 +271,40 @@ def run(
         and (getattr(updater, "AFFINE_PROX", False) or column_affine) \
         and hasattr(data, "margins") and hasattr(data, "eval_from_margins")
     column_tracking = tracking and not getattr(updater, "AFFINE_PROX", False)
+    # One host round trip per trial (docs/KERNELS.md, "Step tail"): a
+    # full-batch tracked run with the simple or squared-L2 updater queues a
+    # whole trial, its f_x included, and fetches one block of scalars:
+    #   [0:5] fused scalars  [5] reg(x)  [6:8] (loss, count) at y
+    #   [8:10] (loss, count) at x  [10] dot_diff (exact-mode trials only)
+    # SPARKAGD_STEP_TAIL=0 keeps the kernel-by-kernel sequence with its four
+    # fetches; the timing-detail diagnostics need that sequence's syncs.
+    step_tail = tracking and not column_tracking and beta < 1.0 \
+        and type(updater) in (SimpleUpdater, SquaredL2Updater) \
+        and os.environ.get("SPARKAGD_STEP_TAIL") != "0" \
+        and os.environ.get("SPARKAGD_TIMING_DETAIL") != "1"
+    tail_block = torch.empty(11, dtype=torch.float64, device=x.device) \
+        if step_tail else None
+    # examples per evaluation: constant in a full-batch run, so fetched at
+    # the first evaluation only and checked at every later fetch
+    eval_count: Optional[float] = None
+
+    def queue_eval(vm, slot, need_grad=True):
+        """eval_from_margins without a host read: the all-reduced
+        (loss, count) goes device-to-device into tail_block[slot:slot+2],
+        the gradient is averaged with the cached count."""
+        nonlocal eval_count
+        grad_sum, loss_count = gradient.eval_from_margins(data, vm, need_grad=need_grad)
+        if grad_sum is not None:
+            comm.allreduce_(grad_sum)
+        comm.allreduce_(loss_count)
+        tail_block[slot:slot + 2].copy_(loss_count)
+        if eval_count is None:
+            eval_count = fetch(loss_count[1])
+        if eval_count > 0 and grad_sum is not None:
+            grad_sum.div_(eval_count)
+        eval_state["n"] += 1
+        return grad_sum
+
     xm = zm = None
     if tracking:
         xm = gradient.margins(data, x)
@@ -273,6 +314,7 @@ def run(
     for n_iter in range(start_iter, num_iterations + 1):
         t_iter0 = time.perf_counter()
         eval_n0, eval_s0 = eval_state["n"], eval_state["seconds"]
+        fetches0 = eval_state["fetches"]
         comm_s0 = _COMM_SECONDS[0]
         if tracking and margin_refresh_every > 0 and n_iter % margin_refresh_every == 0:
             xm = gradient.margins(data, x)
@@ -295,14 +337,21 @@ def run(
             # after a restart gives theta = 1 (AGD.scala:248).
             theta = 2.0 / (1.0 + math.sqrt(1.0 + 4.0 * (L / L_old) / (theta_old * theta_old)))
             y = ops.axpby(1.0 - theta, x_old, theta, z_old)
-            if tracking:
+            step = 1.0 / (theta * L)
+            if step_tail:
+                t_trial0 = time.perf_counter()
+                ym = ops.axpby(1.0 - theta, xm_old, theta, zm_old)
+                g_y = queue_eval(ym, 6)  # A^T·m pass only
+                z, x = ops.at_step_tail(updater.PROX_KIND, x_old, z_old, y, g_y,
+                                        theta, step, reg_param, tail_block[0:6])
+            elif tracking:
                 ym = ops.axpby(1.0 - theta, xm_old, theta, zm_old)
                 f_y, g_y, _count = apply_smooth_margins(ym)  # A^T·m pass only
             else:
                 f_y, g_y, _count = apply_smooth(y)
-            step = 1.0 / (theta * L)
-            z, _ = updater.compute(z_old, g_y, step, 1, reg_param)
-            x = ops.axpby(1.0 - theta, x_old, theta, z)
+            if not step_tail:
+                z, _ = updater.compute(z_old, g_y, step, 1, reg_param)
+                x = ops.axpby(1.0 - theta, x_old, theta, z)
             if tracking:
                 gm = gradient.margins(data, g_y)  # the only other data pass
                 pz = None
@@ -341,15 +390,43 @@ def run(
 
             # Backtracking (AGD.scala:261-292). One fused pass produces all 5
             # iteration scalars (backtracking + convergence + restart).
-            scal = ops.fused_scalars(x, y, g_y, x_old).to("cpu")
+            if step_tail:
+                # f_x (and, past the simple test, g_x and dot_diff) is queued
+                # behind the trial before anything is read; the one fetch
+                # then feeds every decision below. A trial that ends on
+                # xy_sq == 0 has computed its f_x for nothing.
+                if backtrack_simple:
+                    queue_eval(xm, 8, need_grad=False)
+                else:
+                    g_x = queue_eval(xm, 8)
+                    tail_block[10:11].copy_(
+                        ops.dot_diff(x, y, g_x, g_y).reshape(1))
+                scal = tail_block.to("cpu")
+                eval_state["fetches"] += 1
+                eval_state["seconds"] += time.perf_counter() - t_trial0
+                if float(scal[7]) != eval_count or float(scal[9]) != eval_count:
+                    raise RuntimeError(
+                        f"iteration {n_iter}: the evaluation count changed "
+                        f"during the run ({eval_count} at the first "
+                        f"evaluation, now {float(scal[7])} at y and "
+                        f"{float(scal[9])} at x); the gradient was averaged "
+                        "with the first one")
+                f_y = float(scal[6]) / eval_count if eval_count > 0 else float("nan")
+            else:
+                scal = ops.fused_scalars(x, y, g_y, x_old).to("cpu")
+                eval_state["fetches"] += 1
             xy_sq = float(scal[0])
             if xy_sq == 0.0:
                 break
 
+            if step_tail:
+                f_x = float(scal[8]) / eval_count if eval_count > 0 else float("nan")
             if backtrack_simple:
                 # the simple test needs f_x only: loss-only evaluation
                 # (tracking: ZERO data passes — f_x comes from xm)
-                if tracking:
+                if step_tail:
+                    pass
+                elif tracking:
                     f_x, _gx_none, _ = apply_smooth_margins(xm, need_grad=False)
                 else:
                     f_x, _gx_none, _ = apply_smooth(x, need_grad=False)
@@ -357,13 +434,16 @@ def run(
                 q_x = f_y + float(scal[1]) + 0.5 * L * xy_sq
                 localL = L + 2.0 * max(f_x - q_x, 0.0) / xy_sq
                 backtrack_simple = abs(f_y - f_x) >= backtrack_tol * max(abs(f_x), abs(f_y))
+            elif step_tail:
+                f_x_bt = f_x
+                localL = 2.0 * float(scal[10]) / xy_sq
             else:
                 if tracking:
                     f_x, g_x, _ = apply_smooth_margins(xm)
                 else:
                     f_x, g_x, _ = apply_smooth(x)
                 f_x_bt = f_x
-                localL = 2.0 * float(ops.dot_diff(x, y, g_x, g_y)) / xy_sq
+                localL = 2.0 * fetch(ops.dot_diff(x, y, g_x, g_y)) / xy_sq
 
             if localL <= L or L >= Lexact:
                 break
@@ -377,6 +457,7 @@ def run(
 
         if scal is None:
             scal = ops.fused_scalars(x, y, g_y, x_old).to("cpu")
+            eval_state["fetches"] += 1
 
         # Loss history (AGD.scala:296-307). 'exact' reproduces the reference's
         # extra full-data pass at x (TFOCS validation); 'backtrack' reuses the
@@ -386,13 +467,15 @@ def run(
                 f_x2, _g_x2, _ = apply_smooth_margins(xm, need_grad=False)
             else:
                 f_x2, _g_x2, _ = apply_smooth(x, need_grad=False)
-            c_x = float(updater.reg_value(x, reg_param))
+            c_x = float(scal[5]) if step_tail \
+                else fetch(updater.reg_value(x, reg_param))
             loss_history.append(f_x2 + c_x)
         elif loss_history_mode == "backtrack" and f_x_bt is not None:
-            c_x = float(updater.reg_value(x, reg_param))
+            c_x = float(scal[5]) if step_tail \
+                else fetch(updater.reg_value(x, reg_param))
             loss_history.append(f_x_bt + c_x)
         else:
-            c_y = float(updater.reg_value(y, reg_param))
+            c_y = fetch(updater.reg_value(y, reg_param))
             loss_history.append(f_y + c_y)
 
         if math.isnan(f_y) or math.isinf(f_y):
@@ -440,6 +523,7 @@ def run(
                 norm_dx=norm_dx,
                 iter_seconds=time.perf_counter() - t_iter0,
                 n_evals=eval_state["n"] - eval_n0,
+                host_fetches=eval_state["fetches"] - fetches0,
                 eval_seconds=eval_state["seconds"] - eval_s0,
                 **(
                     {"comm_seconds": _COMM_SECONDS[0] - comm_s0}
