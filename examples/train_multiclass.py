@@ -13,6 +13,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 from sparkagd_amd import (SoftmaxRegressionWithAGD, MultinomialModel,
+                          OneVsRestWithAGD,
                           generate_multiclass_problem, evaluation)
 
 dev = "cuda" if torch.cuda.is_available() else "cpu"
@@ -39,3 +40,10 @@ with tempfile.TemporaryDirectory() as d:
     assert torch.equal(model.predict(shard.features).cpu(),
                        reloaded.predict(shard.features).cpu())
 print("model save/load round-trip: ok")
+
+# one-vs-rest with a bias per class: "class c against the rest" has about 1/K
+# positives, a prior a model through the origin cannot represent
+ovr = OneVsRestWithAGD.train(shard, num_classes=K, num_iterations=60,
+                             reg_param=1e-3, intercept=True)
+print(f"one-vs-rest loss: {ovr.loss_history[0]:.4f} -> {ovr.loss_history[-1]:.4f}, "
+      f"intercepts {[round(float(b), 2) for b in ovr.intercepts]}")

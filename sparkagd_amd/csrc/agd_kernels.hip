@@ -1591,37 +1591,7 @@ __global__ __launch_bounds__(BLOCK) void k_at_margin_update(
 // MLlib 1.3; invoked at AGD.scala:215-220).
 // ---------------------------------------------------------------------------
 
-#define PROX_SIMPLE 0
-#define PROX_L1 1
-#define PROX_L2 2
-#define PROX_ELASTIC 3  // l1 soft-threshold then l2 shrink (elastic net)
-
-template <typename T>
-__device__ __forceinline__ T prox_elem(int kind, T wi, T gi, T ts, T tl,
-                                       T tl2, double& racc) {
-  if (kind == PROX_SIMPLE) return wi - ts * gi;
-  if (kind == PROX_L1) {
-    const T w1 = wi - ts * gi;
-    const T aw = fabs(w1) - tl * ts;
-    const T wn = (aw > (T)0) ? ((w1 > (T)0) ? aw : -aw) : (T)0;
-    racc += (double)tl * fabs((double)wn);
-    return wn;
-  }
-  if (kind == PROX_L2) {
-    const T wn = wi * ((T)1 - ts * tl) - ts * gi;
-    racc += 0.5 * (double)tl * (double)wn * (double)wn;
-    return wn;
-  }
-  // PROX_ELASTIC: prox of tl*|w|_1 + tl2/2*|w|^2 —
-  // soft-threshold by ts*tl, then shrink by 1/(1 + ts*tl2)
-  const T w1 = wi - ts * gi;
-  const T aw = fabs(w1) - tl * ts;
-  const T wsoft = (aw > (T)0) ? ((w1 > (T)0) ? aw : -aw) : (T)0;
-  const T wn = wsoft / ((T)1 + ts * tl2);
-  racc += (double)tl * fabs((double)wn) +
-          0.5 * (double)tl2 * (double)wn * (double)wn;
-  return wn;
-}
+// PROX_* and prox_elem (one element of every prox kind): agd_tasks.h
 
 template <typename T>
 __global__ __launch_bounds__(BLOCK) void k_prox(int kind, const T* __restrict__ w,

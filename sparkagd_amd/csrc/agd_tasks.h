@@ -1,9 +1,11 @@
-// Device code shared by the two translation units that hold multi-task
-// multiplier kernels: agd_kernels.hip (one binary label per row, the CV
-// sweep) and agd_tasks_ovr.hip (one-vs-rest: a target class per column).
-// The launch geometry, the binary losses and the per-group evaluation live
-// here, so that both families run the same loss_mult on the same 4-column
-// groups and leave the same partial layout.
+// Device code shared by the translation units that hold multi-task kernels:
+// agd_kernels.hip (one binary label per row, the CV sweep),
+// agd_tasks_ovr.hip (one-vs-rest: a target class per column) and
+// agd_tasks_bias.hip (a bias per task). The launch geometry, the binary
+// losses and the per-group evaluation live here, so that both multiplier
+// families run the same loss_mult on the same 4-column groups and leave the
+// same partial layout; prox_elem, so that the free-row prox runs the element
+// of k_prox_tasks.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -120,3 +122,37 @@ __device__ __forceinline__ void tasks_group(
 // Columns one lane-step of the any-K kernels covers: a wave per row, four
 // columns per lane.
 #define TASKS_CHUNK (WAVE * 4)
+
+// One element of the proximal step, every prox kind (k_prox, k_prox_free,
+// k_prox_tasks in agd_kernels.hip; k_prox_tasks_free in agd_tasks_bias.hip).
+#define PROX_SIMPLE 0
+#define PROX_L1 1
+#define PROX_L2 2
+#define PROX_ELASTIC 3  // l1 soft-threshold then l2 shrink (elastic net)
+
+template <typename T>
+__device__ __forceinline__ T prox_elem(int kind, T wi, T gi, T ts, T tl,
+                                       T tl2, double& racc) {
+  if (kind == PROX_SIMPLE) return wi - ts * gi;
+  if (kind == PROX_L1) {
+    const T w1 = wi - ts * gi;
+    const T aw = fabs(w1) - tl * ts;
+    const T wn = (aw > (T)0) ? ((w1 > (T)0) ? aw : -aw) : (T)0;
+    racc += (double)tl * fabs((double)wn);
+    return wn;
+  }
+  if (kind == PROX_L2) {
+    const T wn = wi * ((T)1 - ts * tl) - ts * gi;
+    racc += 0.5 * (double)tl * (double)wn * (double)wn;
+    return wn;
+  }
+  // PROX_ELASTIC: prox of tl*|w|_1 + tl2/2*|w|^2 —
+  // soft-threshold by ts*tl, then shrink by 1/(1 + ts*tl2)
+  const T w1 = wi - ts * gi;
+  const T aw = fabs(w1) - tl * ts;
+  const T wsoft = (aw > (T)0) ? ((w1 > (T)0) ? aw : -aw) : (T)0;
+  const T wn = wsoft / ((T)1 + ts * tl2);
+  racc += (double)tl * fabs((double)wn) +
+          0.5 * (double)tl2 * (double)wn * (double)wn;
+  return wn;
+}

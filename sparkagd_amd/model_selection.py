@@ -49,7 +49,8 @@ class CVResult:
     the larger lambda); ``fold_weights[l, f]`` are that model's weights [d];
     ``loss_history`` is the stacked run's (sum over the R tasks of mean
     training loss + regulariser); ``model`` is the refit on all rows at
-    ``best_lambda`` (None with ``refit=False``)."""
+    ``best_lambda`` (None with ``refit=False``); ``fold_intercepts[l, f]``
+    is that model's bias (None unless ``intercept=True``)."""
 
     lambdas: List[float]
     heldout_loss: torch.Tensor
@@ -59,6 +60,7 @@ class CVResult:
     fold_weights: torch.Tensor
     loss_history: List[float]
     model: Optional[object] = None
+    fold_intercepts: Optional[torch.Tensor] = None
 
 
 def cross_validate(
@@ -75,6 +77,7 @@ def cross_validate(
     refit: bool = True,
     fold_id: Optional[torch.Tensor] = None,
     pack: bool = False,
+    intercept: bool = False,
 ) -> CVResult:
     """k-fold cross-validation of ``lambdas`` for a binary GLM: all
     ``len(lambdas) * n_folds`` models train in one ``run()`` over the shard,
@@ -107,6 +110,12 @@ def cross_validate(
     copy through the packed MFMA kernels, which carry the f32 weights as a
     bf16 pair. A refused pack leaves the raw route and the reason in
     ``data.pack_refused``. The tracking defaults above do not change.
+
+    ``intercept=True`` fits an unpenalised bias per model (a free last row
+    of the weight block, ``MultiTaskGradient(intercept=True)`` with
+    ``PerTaskUpdater(free_rows=1)``), scores the held-out folds with it and
+    refits with ``intercept=True``: lambda is then selected for the model
+    that is refitted.
     """
     from .optimizer import run
 
@@ -136,7 +145,8 @@ def cross_validate(
     task_lams = [lam for lam in lams for _ in range(n_f)]
     n_tasks = n_l * n_f
     mt_grad = MultiTaskGradient(gradient, n_tasks, fold_id, holdout, comm,
-                                sample_weight=data.sample_weight)
+                                sample_weight=data.sample_weight,
+                                intercept=intercept)
 
     # held-out weight per fold (denominators), all-reduced like the N_r
     sw = data.sample_weight
@@ -151,13 +161,18 @@ def cross_validate(
             f"folds {torch.nonzero(per_fold <= 0).flatten().tolist()} hold "
             "no rows: nothing to score them on")
 
-    if len(set(task_lams)) == 1:
+    if intercept:
+        # the bias row is free at one lambda too
+        run_updater = PerTaskUpdater(updater, task_lams, free_rows=1)
+        reg_param = 1.0
+    elif len(set(task_lams)) == 1:
         # one lambda: the plain updater keeps margin tracking on
         run_updater, reg_param = updater, task_lams[0]
     else:
         run_updater, reg_param = PerTaskUpdater(updater, task_lams), 1.0
     wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
-    w0 = torch.zeros(data.d * n_tasks, device=data.device, dtype=wdtype)
+    w0 = torch.zeros((data.d + int(intercept)) * n_tasks, device=data.device,
+                     dtype=wdtype)
     w, hist = run(
         data, mt_grad, run_updater, cfg.convergence_tol, cfg.num_iterations,
         reg_param, w0, cfg.L0, cfg.Lexact, cfg.beta, cfg.alpha,
@@ -176,7 +191,9 @@ def cross_validate(
     std = heldout.std(dim=1, unbiased=False)
     best_val = float(mean.min())
     best = max(lam for lam, m in zip(lams, mean.tolist()) if m == best_val)
-    fold_w = w.reshape(data.d, n_tasks).T.reshape(n_l, n_f, data.d).contiguous()
+    n_w = data.d * n_tasks
+    fold_w = w[:n_w].reshape(data.d, n_tasks).T.reshape(n_l, n_f, data.d).contiguous()
+    fold_b = w[n_w:].reshape(n_l, n_f).clone() if intercept else None
 
     model = None
     if refit:
@@ -188,5 +205,7 @@ def cross_validate(
         model = trainer.train(
             data, num_iterations=num_iterations, reg_param=best,
             convergence_tol=convergence_tol, updater=updater, comm=comm,
-            config=dataclasses.replace(cfg))
-    return CVResult(lams, heldout, mean, std, best, fold_w, hist, model)
+            config=dataclasses.replace(cfg),
+            **({"intercept": True} if intercept else {}))
+    return CVResult(lams, heldout, mean, std, best, fold_w, hist, model,
+                    fold_b)

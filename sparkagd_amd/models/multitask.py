@@ -49,6 +49,14 @@ class MultiTaskGradient(Gradient):
     target_class[r]]``. Without ``fold_id`` every scale is 1 and the objective
     is the sum of the R mean losses and regularisers, whose minimiser is the
     stack of the R one-vs-rest minimisers.
+
+    ``intercept=True`` fits an unpenalised bias per task: the weights are
+    the flat [(d+1), R] block whose last row (the last R entries) holds the
+    biases. The data passes run on the [d, R] prefix view as they are; the
+    margins gain ``1·bᵀ`` (``add_bias_cols``, biases read on the device) and
+    the gradient's last row is ``sum_i M[i, :]`` (``colsum_multi``). Pair it
+    with ``PerTaskUpdater(..., free_rows=1)``. The shard stays a plain dense
+    or CSR shard (``InterceptShard`` carries ONE bias and is refused).
     """
 
     IS_MULTICLASS = True  # [n, KC] margins, shard left raw by the pack policy
@@ -58,7 +66,8 @@ class MultiTaskGradient(Gradient):
                  fold_id: Optional[torch.Tensor] = None,
                  holdout: Optional[Sequence[int]] = None, comm=None,
                  sample_weight: Optional[torch.Tensor] = None,
-                 target_class: Optional[Sequence[int]] = None):
+                 target_class: Optional[Sequence[int]] = None,
+                 intercept: bool = False):
         if getattr(base, "IS_MULTICLASS", False) or getattr(base, "LOSS_TYPE", -1) < 0:
             raise ValueError("base must be one of the binary gradients")
         if num_tasks < 1:
@@ -67,6 +76,7 @@ class MultiTaskGradient(Gradient):
         self.LOSS_TYPE = base.LOSS_TYPE
         self.num_tasks = int(num_tasks)
         self.num_classes = self.num_tasks
+        self.intercept = bool(intercept)
         self.fold_id = None
         self.holdout = None
         self.target_class = None
@@ -187,7 +197,15 @@ class MultiTaskGradient(Gradient):
         keeps the f32 weights of a bf16 dense shard (split into two bf16
         GEMM operands) where the training route rounds them to bf16."""
         self._check_shard(shard)
-        return mc.multi_margins(shard, v, self.num_tasks, scoring)
+        if not self.intercept:
+            return mc.multi_margins(shard, v, self.num_tasks, scoring)
+        nw = shard.d * self.num_tasks
+        if v.numel() != nw + self.num_tasks:
+            raise ValueError(
+                f"weights [{v.numel()}] are not the [({shard.d} + 1), "
+                f"{self.num_tasks}] block of an intercept run")
+        zm = mc.multi_margins(shard, v[:nw], self.num_tasks, scoring)
+        return mt.add_bias_cols(zm, 1.0, v, nw, self.num_tasks)
 
     def task_losses(self, shard, margins, mask=None, invert=False):
         """(task_loss f64 [R], loss_count f64 [2]) of the local rows from
@@ -218,7 +236,17 @@ class MultiTaskGradient(Gradient):
             self.last_task_loss = task_loss
             return None, lc
         m, lc = self.multiplier_loss(shard, margins, mask)
-        return mc.multi_grad(shard, m, self.num_tasks), lc
+        gw = mc.multi_grad(shard, m, self.num_tasks)
+        if not self.intercept:
+            return gw, lc
+        # [(d+1), R]: Aᵀ·M, then the column sums of M written to the last
+        # row on the device (scales, folds, masks and weights are inside M)
+        g = torch.empty(gw.numel() + self.num_tasks, dtype=gw.dtype,
+                        device=gw.device)
+        g[:gw.numel()].copy_(gw)
+        mt.colsum_multi(m, self.num_tasks, tail=g[gw.numel():],
+                        want_f64=False)
+        return g, lc
 
     def eval(self, shard, w, mask=None, need_grad=True):
         return self.eval_from_margins(shard, self.margins(shard, w), mask,
@@ -243,11 +271,20 @@ class PerTaskUpdater(Updater):
     ``MultiTaskGradient`` run through ``prox_margins_tasks`` (two shard
     streams per step, as with one lambda; on a bf16 dense GPU shard only with
     ``track_margins=True``, see ``MultiTaskGradient.rounds_margin_weights``).
-    L1 and elastic-net bases are not affine and run untracked."""
+    L1 and elastic-net bases are not affine and run untracked.
+
+    ``free_rows=1``: the weights are the [(d+1), R] block of a
+    ``MultiTaskGradient(intercept=True)`` run and its last row, the biases,
+    is not regularised: it takes the plain step for every base, stays out of
+    the regularisation value, and the tracked margin update carries the
+    free-row term (``prox_margins_tasks(..., z_old=...)``)."""
 
     AFFINE_PROX = False
 
-    def __init__(self, base: Updater, lambdas: Sequence[float]):
+    def __init__(self, base: Updater, lambdas: Sequence[float],
+                 free_rows: int = 0):
+        if free_rows not in (0, 1):
+            raise ValueError("free_rows is 0 or 1 (one bias per task)")
         if isinstance(base, (PerTaskUpdater, FreeTailUpdater)) or base.PROX_KIND < 0:
             raise ValueError("base must be one of the four plain updaters")
         lam = torch.as_tensor(lambdas, dtype=torch.float64).reshape(-1).cpu()
@@ -257,6 +294,11 @@ class PerTaskUpdater(Updater):
         self.PROX_KIND = base.PROX_KIND
         self.lambdas = lam
         self.num_tasks = lam.numel()
+        self.free_rows = int(free_rows)
+        #: with a bias row and ONE lambda this is the plain updater's run:
+        #: the optimizer tracks margins by default on every shard kind
+        self.tracks_like_one_lambda = bool(
+            self.free_rows and bool((lam == lam[0]).all()))
         #: the prox is affine in (w, g) column by column (see the class doc)
         self.COLUMN_AFFINE_PROX = type(base) in (SimpleUpdater, SquaredL2Updater)
         self._cache = {}
@@ -287,19 +329,28 @@ class PerTaskUpdater(Updater):
                 f"{self.num_tasks}] block")
         lam, lam2 = self._lams(reg_param, weights_old.device)
         return mt.prox_tasks(self.PROX_KIND, weights_old, gradient,
-                             step_size / math.sqrt(iter), lam, lam2)
+                             step_size / math.sqrt(iter), lam, lam2,
+                             n_free=self.free_rows * self.num_tasks)
 
-    def prox_margins_tasks(self, zm_old, xm_old, gm, step, reg_param, theta):
+    def prox_margins_tasks(self, zm_old, xm_old, gm, step, reg_param, theta,
+                           z_old=None):
         """(zm', xm') of the padded [n*KC] margins after the prox step
         ``compute`` takes at ``step`` and the AT interpolation at ``theta``;
         only valid when ``COLUMN_AFFINE_PROX``. The lambdas are the cached
-        device vector of ``compute``: the step copies nothing to the device."""
+        device vector of ``compute``: the step copies nothing to the device.
+        With ``free_rows`` the bias row of ``z_old`` (the weights the step
+        starts from) is read on the device for the free-row term."""
         if not self.COLUMN_AFFINE_PROX:
             raise NotImplementedError(
                 f"PerTaskUpdater({type(self.base).__name__}) has no affine prox")
         lam, _ = self._lams(reg_param, zm_old.device)
+        offset = None
+        if self.free_rows:
+            if z_old is None:
+                raise ValueError("a free-row updater needs z_old")
+            offset = (z_old, z_old.numel() - self.num_tasks)
         return mt.at_margin_update_tasks(zm_old, xm_old, gm, step, lam, theta,
-                                         self.num_tasks)
+                                         self.num_tasks, offset=offset)
 
     def reg_value(self, weights, reg_param):
         return self.compute(weights, torch.zeros_like(weights), 0.0, 1,

@@ -459,11 +459,18 @@ class SoftmaxRegressionWithAGD:
 class OneVsRestModel:
     """K one-vs-rest binary models over the same features: weights [d, K],
     column c scoring "class c against the rest". ``predict`` is the argmax of
-    the margins, the lowest class index winning ties."""
+    the margins, the lowest class index winning ties. ``intercepts`` [K] are
+    the per-class biases (zeros for a model trained without)."""
 
     def __init__(self, weights: torch.Tensor, loss_history, num_classes: int,
-                 link: str):
+                 link: str, intercepts: Optional[torch.Tensor] = None):
         self.weights = weights.reshape(-1, int(num_classes))
+        if intercepts is None:
+            intercepts = torch.zeros(int(num_classes), dtype=weights.dtype,
+                                     device=weights.device)
+        elif intercepts.numel() != int(num_classes):
+            raise ValueError("intercepts must hold one bias per class")
+        self.intercepts = intercepts.reshape(-1)
         self.loss_history = list(loss_history)
         self.num_classes = int(num_classes)
         self.link = link
@@ -471,12 +478,17 @@ class OneVsRestModel:
     def score(self, shard) -> torch.Tensor:
         """Margins [n, K] of a whole dense or CSR shard through the
         multi-column margins pass (scoring route: f32 weights are kept on a
-        bf16 shard); the features are read in place."""
+        bf16 shard); the features are read in place. The intercepts are
+        added on the device (``add_bias_cols``)."""
         from ..ops.multiclass import multi_margins, padded_k
+        from ..ops.multitask import add_bias_cols
 
         k = self.num_classes
         w = _weights_for(shard, self.weights.reshape(-1))
         zp = multi_margins(shard, w, k, scoring=True)
+        if bool((self.intercepts != 0).any()):
+            b = self.intercepts.to(device=zp.device, dtype=zp.dtype)
+            zp = add_bias_cols(zp, 1.0, b, 0, k)
         return zp.reshape(shard.n, padded_k(k))[:, :k]
 
     def predict(self, shard) -> torch.Tensor:
@@ -489,15 +501,19 @@ class OneVsRestModel:
     def save(self, path: str) -> None:
         _save_model(path, self.weights,
                     {"kind": "one_vs_rest", "num_classes": self.num_classes,
-                     "link": self.link, "loss_history": self.loss_history})
+                     "link": self.link, "loss_history": self.loss_history,
+                     "intercepts": [float(b) for b in self.intercepts.tolist()]})
 
     @classmethod
     def load(cls, path: str, device=None) -> "OneVsRestModel":
         w, meta = _load_model(path, device)
         if meta.get("kind") != "one_vs_rest":
             raise ValueError(f"not a OneVsRestModel checkpoint: {meta.get('kind')}")
+        b = meta.get("intercepts")  # absent in older checkpoints: zeros
+        if b is not None:
+            b = torch.tensor(b, dtype=w.dtype, device=w.device)
         return cls(w, meta.get("loss_history", []), meta["num_classes"],
-                   meta["link"])
+                   meta["link"], b)
 
 
 def _check_class_labels(data, num_classes: int, comm: Communicator) -> None:
@@ -538,6 +554,8 @@ class OneVsRestWithAGD:
         comm: Optional[Communicator] = None,
         config: Optional[AGDConfig] = None,
         pack: bool = False,
+        intercept: bool = False,
+        initial_intercepts: Optional[torch.Tensor] = None,
     ) -> OneVsRestModel:
         """``data`` is a dense (f32, bf16, fp8, packed) or CSR shard whose
         labels are class indices in [0, num_classes); a shard per rank with
@@ -545,7 +563,11 @@ class OneVsRestWithAGD:
         squared-L2 or simple ``updater`` still tracks its margins where
         ``MultiTaskGradient.rounds_margin_weights`` allows).
         ``initial_weights`` is the flat [d * num_classes] block. ``pack=True``
-        packs a dense GPU shard first, as in ``SoftmaxRegressionWithAGD``."""
+        packs a dense GPU shard first, as in ``SoftmaxRegressionWithAGD``.
+        ``intercept=True`` fits an unpenalised bias per class (started from
+        ``initial_intercepts`` [num_classes], zeros by default): "class c
+        against the rest" has about 1/K positives, a prior a model through
+        the origin cannot represent."""
         from ..optimizer import run
         from .multitask import MultiTaskGradient, PerTaskUpdater
 
@@ -578,20 +600,36 @@ class OneVsRestWithAGD:
                              "(config.solver='gram' is not supported)")
         if updater is None:
             updater = SquaredL2Updater() if bool((lams > 0).any()) else SimpleUpdater()
-        if lams.numel() == 1 or len(set(lams.tolist())) == 1:
+        if initial_intercepts is not None and not intercept:
+            raise ValueError("initial_intercepts needs intercept=True")
+        if intercept:
+            # the bias row is free whatever the lambdas are: at equal lambdas
+            # too the run goes through the per-task updater
+            run_updater = PerTaskUpdater(
+                updater, lams.expand(k).tolist(), free_rows=1)
+            run_reg = 1.0
+        elif lams.numel() == 1 or len(set(lams.tolist())) == 1:
             run_updater, run_reg = updater, float(lams[0])
         else:
             run_updater, run_reg = PerTaskUpdater(updater, lams.tolist()), 1.0
         grad_cls, link = cls.LOSSES[loss]
         grad = MultiTaskGradient(grad_cls(), k, comm=comm,
                                  sample_weight=data.sample_weight,
-                                 target_class=range(k))
+                                 target_class=range(k), intercept=intercept)
         if initial_weights is None:
             wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
             initial_weights = torch.zeros(data.d * k, device=data.device,
                                           dtype=wdtype)
         elif initial_weights.numel() != data.d * k:
             raise ValueError(f"initial_weights must hold [{data.d}, {k}]")
+        if intercept:
+            b0 = torch.zeros(k) if initial_intercepts is None else initial_intercepts
+            if b0.numel() != k:
+                raise ValueError(f"initial_intercepts must hold [{k}]")
+            initial_weights = torch.cat([
+                initial_weights.reshape(-1),
+                b0.reshape(-1).to(device=initial_weights.device,
+                                  dtype=initial_weights.dtype)])
         w, hist = run(
             data, grad, run_updater, cfg.convergence_tol, cfg.num_iterations,
             run_reg, initial_weights.reshape(-1), cfg.L0, cfg.Lexact, cfg.beta,
@@ -600,6 +638,9 @@ class OneVsRestWithAGD:
             track_margins=cfg.track_margins,
             margin_refresh_every=cfg.margin_refresh_every,
             backtrack_tol=cfg.backtrack_tol)
+        if intercept:
+            return OneVsRestModel(w[:data.d * k], hist, k, link,
+                                  w[data.d * k:].clone())
         return OneVsRestModel(w, hist, k, link)
 
 

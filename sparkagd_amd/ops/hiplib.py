@@ -177,6 +177,19 @@ def load() -> ctypes.CDLL:
     lib.agd_at_margin_update_tasks.restype = I
     lib.agd_at_margin_update_tasks.argtypes = [P, P, P, D, P, D, LL, I, I, I,
                                                P, P, P]
+    # per-task bias kernels (csrc/agd_tasks_bias.hip)
+    lib.agd_colsum_ws_doubles.restype = LL
+    lib.agd_colsum_ws_doubles.argtypes = [I]
+    lib.agd_colsum_multi.restype = I
+    lib.agd_colsum_multi.argtypes = [P, LL, I, I, I, P, P, P, P]
+    lib.agd_add_bias_cols.restype = I
+    lib.agd_add_bias_cols.argtypes = [P, D, P, LL, LL, I, I, I, P]
+    lib.agd_at_margin_update_tasks_off.restype = I
+    lib.agd_at_margin_update_tasks_off.argtypes = [P, P, P, D, P, D, P, LL, LL,
+                                                   I, I, I, P, P, P]
+    lib.agd_prox_tasks_free.restype = I
+    lib.agd_prox_tasks_free.argtypes = [I, P, P, D, P, P, I, P, P, LL, LL, I,
+                                        P, P]
 
     _lib = lib
     return lib
@@ -860,33 +873,62 @@ def multiplier_tasks(
 
 
 def prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
-               lam: torch.Tensor, lam2: torch.Tensor
+               lam: torch.Tensor, lam2: torch.Tensor, n_free: int = 0
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """``prox`` over the flat feature-major [d, R] block with task r's
-    (lam[r], lam2[r]); lam / lam2 are f64 [R] on w's device."""
+    (lam[r], lam2[r]); lam / lam2 are f64 [R] on w's device. ``n_free`` > 0:
+    the last ``n_free`` elements (the bias row) take the plain step and stay
+    out of the regularisation value (k_prox_tasks_free)."""
     lib = load()
     r = lam.numel()
     if lam2.numel() != r or w.numel() % r != 0:
         raise ValueError("prox_tasks: weights must be [d * R] with lam, lam2 [R]")
+    if not 0 <= n_free <= w.numel():
+        raise ValueError(f"n_free {n_free} outside [0, {w.numel()}]")
     lam = lam.to(device=w.device, dtype=torch.float64).contiguous()
     lam2 = lam2.to(device=w.device, dtype=torch.float64).contiguous()
     out = torch.empty_like(w)
     reg = torch.zeros((), dtype=torch.float64, device=w.device)
-    rc = lib.agd_prox_tasks(kind, _ptr(w.contiguous()), _ptr(g.contiguous()),
-                            float(step), _ptr(lam), _ptr(lam2), r, _ptr(out),
-                            _ptr(reg), w.numel(), _VEC_DTYPE[w.dtype],
-                            _ptr(_red_ws(w.device)), _stream(w))
+    if n_free:
+        rc = lib.agd_prox_tasks_free(
+            kind, _ptr(w.contiguous()), _ptr(g.contiguous()), float(step),
+            _ptr(lam), _ptr(lam2), r, _ptr(out), _ptr(reg), w.numel(),
+            int(n_free), _VEC_DTYPE[w.dtype], _ptr(_red_ws(w.device)),
+            _stream(w))
+    else:
+        rc = lib.agd_prox_tasks(kind, _ptr(w.contiguous()),
+                                _ptr(g.contiguous()), float(step), _ptr(lam),
+                                _ptr(lam2), r, _ptr(out), _ptr(reg), w.numel(),
+                                _VEC_DTYPE[w.dtype], _ptr(_red_ws(w.device)),
+                                _stream(w))
     _check(rc)
     return out, reg
 
 
+def _bias_cols_src(src: torch.Tensor, idx0: int, r: int,
+                   like: torch.Tensor) -> torch.Tensor:
+    """The device vector R biases are read from at ``idx0``, checked against
+    the margins they are applied to (same dtype and device, range inside)."""
+    if src.dtype != like.dtype or src.device != like.device:
+        raise TypeError(
+            f"bias source ({src.dtype}, {src.device}) must match the margins "
+            f"({like.dtype}, {like.device})")
+    if idx0 < 0 or idx0 + r > src.numel():
+        raise IndexError(
+            f"biases [{idx0}, {idx0 + r}) outside [0, {src.numel()})")
+    return src.contiguous()
+
+
 def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
                            gm: torch.Tensor, step: float, lam: torch.Tensor,
-                           theta: float, num_tasks: int, kc: int):
+                           theta: float, num_tasks: int, kc: int,
+                           offset: Optional[Tuple[torch.Tensor, int]] = None):
     """(zm_new, xm_new) of the padded [n*kc] margins with task r's shrink
     ``1 - step*lam[r]`` (k_at_margin_update_tasks); pad columns come out as
     exact zeros. lam is f64 [R]: already on the device it is used as it is
-    (no copy, no synchronisation)."""
+    (no copy, no synchronisation). ``offset = (z_old, idx0)``: the free-row
+    term ``(step*lam[r]) * z_old[idx0 + r]`` is added to column r, the biases
+    read on the device (k_at_margin_update_tasks_off)."""
     lib = load()
     total = zm_old.numel()
     if total % kc != 0 or xm_old.numel() != total or gm.numel() != total:
@@ -899,13 +941,70 @@ def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
     lam = lam.to(device=zm_old.device, dtype=torch.float64).contiguous()
     zm_new = torch.empty_like(zm_old)
     xm_new = torch.empty_like(xm_old)
-    rc = lib.agd_at_margin_update_tasks(
-        _ptr(zm_old.contiguous()), _ptr(xm_old.contiguous()),
-        _ptr(gm.contiguous()), float(step), _ptr(lam), float(theta),
-        total // kc, int(num_tasks), int(kc), _VEC_DTYPE[zm_old.dtype],
-        _ptr(zm_new), _ptr(xm_new), _stream(zm_old))
+    head = (_ptr(zm_old.contiguous()), _ptr(xm_old.contiguous()),
+            _ptr(gm.contiguous()), float(step), _ptr(lam), float(theta))
+    tail = (total // kc, int(num_tasks), int(kc), _VEC_DTYPE[zm_old.dtype],
+            _ptr(zm_new), _ptr(xm_new), _stream(zm_old))
+    if offset is None:
+        rc = lib.agd_at_margin_update_tasks(*head, *tail)
+    else:
+        src = _bias_cols_src(offset[0], int(offset[1]), num_tasks, zm_old)
+        rc = lib.agd_at_margin_update_tasks_off(*head, _ptr(src),
+                                                int(offset[1]), *tail)
     _check(rc)
     return zm_new, xm_new
+
+
+_colsum_ws_cache = {}
+
+
+def colsum_multi(m_padded_flat: torch.Tensor, num_tasks: int, kc: int,
+                 tail: Optional[torch.Tensor] = None, want_f64: bool = True
+                 ) -> Optional[torch.Tensor]:
+    """Column sums of the padded f32 multiplier [n*kc], accumulated in f64
+    (k_colsum_multi). ``tail``: a contiguous R-entry f32 / f64 view (the last
+    row of the gradient block) the sums are written to in its dtype. Returns
+    the f64 [R] sums when ``want_f64``."""
+    lib = load()
+    dev = m_padded_flat.device
+    if m_padded_flat.dtype != torch.float32 or m_padded_flat.numel() % kc:
+        raise TypeError("colsum_multi: the multiplier is the f32 [n*kc] flat")
+    if tail is not None and (tail.numel() != num_tasks
+                             or not tail.is_contiguous()
+                             or tail.device != dev):
+        raise ValueError("colsum_multi: tail must be a contiguous [R] view "
+                         "on the multiplier's device")
+    ws = _colsum_ws_cache.get((dev, kc))
+    if ws is None:
+        ws = torch.empty(int(lib.agd_colsum_ws_doubles(kc)),
+                         dtype=torch.float64, device=dev)
+        _colsum_ws_cache[(dev, kc)] = ws
+    out = (torch.empty(num_tasks, dtype=torch.float64, device=dev)
+           if want_f64 else None)
+    rc = lib.agd_colsum_multi(
+        _ptr(m_padded_flat.contiguous()), m_padded_flat.numel() // kc,
+        int(num_tasks), int(kc),
+        _VEC_DTYPE[tail.dtype] if tail is not None else 1, _ptr(tail),
+        _ptr(out), _ptr(ws), _stream(m_padded_flat))
+    _check(rc)
+    return out
+
+
+def add_bias_cols_(z_padded_flat: torch.Tensor, coef: float,
+                   src: torch.Tensor, idx0: int, num_tasks: int,
+                   kc: int) -> torch.Tensor:
+    """In place Z[i, c] += coef * src[idx0 + c] for c < R on the padded
+    [n*kc] flat, the biases read on the device (k_add_bias_cols)."""
+    lib = load()
+    if not z_padded_flat.is_contiguous() or z_padded_flat.numel() % kc:
+        raise ValueError("add_bias_cols_ needs the contiguous [n*kc] flat")
+    src = _bias_cols_src(src, int(idx0), num_tasks, z_padded_flat)
+    rc = lib.agd_add_bias_cols(
+        _ptr(z_padded_flat), float(coef), _ptr(src), int(idx0),
+        z_padded_flat.numel() // kc, int(num_tasks), int(kc),
+        _VEC_DTYPE[z_padded_flat.dtype], _stream(z_padded_flat))
+    _check(rc)
+    return z_padded_flat
 
 
 def dense_grad_multi(features: torch.Tensor, m_padded_flat: torch.Tensor,

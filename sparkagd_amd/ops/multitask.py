@@ -154,6 +154,64 @@ def ref_at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
     return zm_new.reshape(-1), xm_new.reshape(-1)
 
 
+def ref_colsum_multi(m_padded_flat: torch.Tensor, num_tasks: int
+                     ) -> torch.Tensor:
+    """f64 [R] column sums of the padded [n*KC] multiplier."""
+    kc = padded_k(num_tasks)
+    return (m_padded_flat.reshape(-1, kc)[:, :num_tasks]
+            .to(torch.float64).sum(dim=0))
+
+
+def ref_add_bias_cols(z_padded_flat: torch.Tensor, coef: float,
+                      src: torch.Tensor, idx0: int, num_tasks: int
+                      ) -> torch.Tensor:
+    """In place Z[:, c] += coef * src[idx0 + c] for c < R, the product
+    rounded in Z's dtype; pad columns are not touched."""
+    kc = padded_k(num_tasks)
+    z = z_padded_flat.view(-1, kc)
+    b = src[idx0:idx0 + num_tasks].to(z.dtype)
+    z[:, :num_tasks] += (coef * b).unsqueeze(0)
+    return z_padded_flat
+
+
+def ref_at_margin_update_tasks_off(zm_old: torch.Tensor, xm_old: torch.Tensor,
+                                   gm: torch.Tensor, step: float,
+                                   lam: torch.Tensor, theta: float,
+                                   num_tasks: int, z_old: torch.Tensor,
+                                   idx0: int
+                                   ) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ref_at_margin_update_tasks`` with a free bias row:
+
+        zm'[:, r] = pz_r*zm[:, r] - step*gm[:, r] + (1 - pz_r)*z_old[idx0 + r]
+
+    with pz_r = 1 - step*lam[r] and 1 - pz_r formed in f64 and cast."""
+    kc = padded_k(num_tasks)
+    n = zm_old.numel() // kc
+    dt = zm_old.dtype
+    pz64 = 1.0 - step * lam.to(device=zm_old.device, dtype=torch.float64)
+    pz = pz64.to(dt)
+    omp = (1.0 - pz64).to(dt)
+    zb = z_old[idx0:idx0 + num_tasks].to(dt)
+    live = slice(0, num_tasks)
+    zm_new = torch.zeros((n, kc), dtype=dt, device=zm_old.device)
+    xm_new = torch.zeros((n, kc), dtype=dt, device=zm_old.device)
+    zn = (pz.unsqueeze(0) * zm_old.reshape(n, kc)[:, live]
+          - step * gm.reshape(n, kc)[:, live] + (omp * zb).unsqueeze(0))
+    zm_new[:, live] = zn
+    xm_new[:, live] = (1.0 - theta) * xm_old.reshape(n, kc)[:, live] + theta * zn
+    return zm_new.reshape(-1), xm_new.reshape(-1)
+
+
+def ref_prox_tasks_free(kind: int, w: torch.Tensor, g: torch.Tensor,
+                        step: float, lam: torch.Tensor, lam2: torch.Tensor,
+                        n_free: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``ref_prox_tasks`` on all but the last ``n_free`` elements, which take
+    ``w - step*g`` and add nothing to the regularisation value."""
+    n_reg = w.numel() - n_free
+    head, reg = ref_prox_tasks(kind, w[:n_reg], g[:n_reg], step, lam, lam2)
+    return torch.cat([head, w[n_reg:] - step * g[n_reg:]]), reg
+
+
 # --- dispatch (GPU -> HIP kernels via hiplib; CPU -> oracle) ---
 
 def multiplier_tasks(
@@ -192,29 +250,73 @@ def multiplier_tasks(
 
 
 def prox_tasks(kind: int, w: torch.Tensor, g: torch.Tensor, step: float,
-               lam: torch.Tensor, lam2: torch.Tensor
+               lam: torch.Tensor, lam2: torch.Tensor, n_free: int = 0
                ) -> Tuple[torch.Tensor, torch.Tensor]:
     """One proximal step of every task + the summed regularisation value;
-    ``lam`` / ``lam2`` are [R] (f64)."""
+    ``lam`` / ``lam2`` are [R] (f64). ``n_free``: the last ``n_free`` elements
+    of the flat block (the bias row of a [(d+1), R] block: ``n_free = R``)
+    take the plain step ``w - step*g`` and are not regularised."""
+    if not 0 <= n_free <= w.numel() or (w.numel() - n_free) % lam.numel():
+        raise ValueError(
+            f"prox_tasks: [{w.numel()}] weights with {n_free} free elements "
+            f"are not a [d, {lam.numel()}] block")
     if _use_hip(w):
-        return hiplib.prox_tasks(kind, w, g, step, lam, lam2)
+        return hiplib.prox_tasks(kind, w, g, step, lam, lam2, n_free)
+    if n_free:
+        return ref_prox_tasks_free(kind, w, g, step, lam, lam2, n_free)
     return ref_prox_tasks(kind, w, g, step, lam, lam2)
 
 
 def at_margin_update_tasks(zm_old: torch.Tensor, xm_old: torch.Tensor,
                            gm: torch.Tensor, step: float, lam: torch.Tensor,
-                           theta: float, num_tasks: int
+                           theta: float, num_tasks: int,
+                           offset: Optional[Tuple[torch.Tensor, int]] = None
                            ) -> Tuple[torch.Tensor, torch.Tensor]:
     """Fused AT margin update of a multi-task run whose prox is affine per
     column (simple: ``lam`` zeros; squared L2): (zm', xm') from the padded
     [n*KC] margins of z, x and the gradient in one pass; ``lam`` is [R]
-    (f64). Pad columns of the outputs are exact zeros."""
+    (f64). Pad columns of the outputs are exact zeros. ``offset = (z_old,
+    idx0)``: the weights carry an unpenalised bias row at ``idx0`` and column
+    r gains ``step*lam[r] * z_old[idx0 + r]``, read on the device."""
     if lam.numel() != num_tasks:
         raise ValueError(f"lam has {lam.numel()} entries for {num_tasks} tasks")
     if _use_hip(zm_old):
         return hiplib.at_margin_update_tasks(zm_old, xm_old, gm, step, lam,
                                              theta, num_tasks,
-                                             padded_k(num_tasks))
+                                             padded_k(num_tasks), offset)
+    if offset is not None:
+        return ref_at_margin_update_tasks_off(zm_old, xm_old, gm, step, lam,
+                                              theta, num_tasks, offset[0],
+                                              int(offset[1]))
     return ref_at_margin_update_tasks(zm_old, xm_old, gm, step, lam, theta,
                                       num_tasks)
 
+
+def colsum_multi(m_padded_flat: torch.Tensor, num_tasks: int,
+                 tail: Optional[torch.Tensor] = None, want_f64: bool = True
+                 ) -> Optional[torch.Tensor]:
+    """``sum_i M[i, c]`` for c < R of the padded [n*KC] multiplier,
+    accumulated in f64: the bias row of the gradient. ``tail`` (a contiguous
+    [R] view, the last row of the gradient block) receives the sums in its
+    dtype; the f64 [R] sums are returned when ``want_f64``."""
+    if _use_hip(m_padded_flat):
+        return hiplib.colsum_multi(m_padded_flat, num_tasks,
+                                   padded_k(num_tasks), tail, want_f64)
+    sums = ref_colsum_multi(m_padded_flat, num_tasks)
+    if tail is not None:
+        tail.copy_(sums)
+    return sums if want_f64 else None
+
+
+def add_bias_cols(z_padded_flat: torch.Tensor, coef: float, src: torch.Tensor,
+                  idx0: int, num_tasks: int) -> torch.Tensor:
+    """In place ``Z[i, c] += coef * src[idx0 + c]`` for c < R on the padded
+    [n*KC] margins; ``src`` is the weight vector the biases live in. Pad
+    columns are left as they are."""
+    if idx0 < 0 or idx0 + num_tasks > src.numel():
+        raise IndexError(
+            f"biases [{idx0}, {idx0 + num_tasks}) outside [0, {src.numel()})")
+    if _use_hip(z_padded_flat):
+        return hiplib.add_bias_cols_(z_padded_flat, coef, src, idx0,
+                                     num_tasks, padded_k(num_tasks))
+    return ref_add_bias_cols(z_padded_flat, coef, src, idx0, num_tasks)

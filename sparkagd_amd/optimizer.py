@@ -263,9 +263,12 @@ def run(
         and getattr(gradient, "IS_MULTITASK", False) \
         and getattr(gradient, "num_tasks", None) == getattr(updater, "num_tasks", -1)
     if column_affine and track_margins == "auto" \
-            and gradient.rounds_margin_weights(data):
+            and gradient.rounds_margin_weights(data) \
+            and not getattr(updater, "tracks_like_one_lambda", False):
         # bf16 GEMM margins: the default stays untracked (see
-        # MultiTaskGradient.rounds_margin_weights); track_margins=True opts in
+        # MultiTaskGradient.rounds_margin_weights); track_margins=True opts
+        # in. A free-row PerTaskUpdater at ONE lambda is the plain updater
+        # with a bias row and is tracked by default as that one is.
         column_affine = False
     tracking = bool(track_margins) \
         and (getattr(updater, "AFFINE_PROX", False) or column_affine) \
@@ -363,8 +366,16 @@ def run(
                 if column_tracking:
                     # zm' and xm' in one pass with a shrink per task
                     # (k_at_margin_update_tasks)
-                    zm, xm = updater.prox_margins_tasks(
-                        zm_old, xm_old, gm, step, reg_param, theta)
+                    if getattr(updater, "free_rows", 0):
+                        # unpenalised bias row: column r gains
+                        # (1 - pz_r)·z_b[r], z_b read on device from z_old
+                        # (k_at_margin_update_tasks_off)
+                        zm, xm = updater.prox_margins_tasks(
+                            zm_old, xm_old, gm, step, reg_param, theta,
+                            z_old=z_old)
+                    else:
+                        zm, xm = updater.prox_margins_tasks(
+                            zm_old, xm_old, gm, step, reg_param, theta)
                 elif pz is not None:
                     # fused: zm' and xm' in one pass (k_at_margin_update) —
                     # one launch + one fewer read stream than the
