@@ -23,6 +23,35 @@ import torch
 from . import ops
 
 
+#: shard kinds that serve ``sample_rows`` (row-sampled mini-batch passes)
+SAMPLE_ROWS_KINDS = "a resident DenseShard (bf16 / f32 / f64 / fp8), or an InterceptShard over one"
+
+
+def check_sample_rows(shard, gradient=None) -> None:
+    """Raise ``ValueError`` unless ``shard`` (and ``gradient``, if given)
+    serves ``sample_rows=True``."""
+    if gradient is not None and (getattr(gradient, "IS_MULTICLASS", False)
+                                 or getattr(gradient, "LOSS_TYPE", -1) < 0):
+        raise ValueError(
+            f"sample_rows=True is not supported with {type(gradient).__name__}: "
+            f"it needs a binary loss on {SAMPLE_ROWS_KINDS}")
+    kind = getattr(shard, "kind", None)
+    if kind == "intercept":
+        kind = getattr(shard.inner, "kind", None)
+    if kind != "dense":
+        raise ValueError(
+            f"sample_rows=True is not supported on {type(shard).__name__}: "
+            f"it needs {SAMPLE_ROWS_KINDS}")
+
+
+def _expected_rows(sample_rows, n: int) -> int:
+    """List length to plan for: ceil(f * n) when ``sample_rows`` is the
+    sampling fraction, the whole shard when it is just ``True``."""
+    if sample_rows is True or not 0.0 < float(sample_rows) < 1.0:
+        return n
+    return max(1, min(n, math.ceil(float(sample_rows) * n)))
+
+
 class DenseShard:
     """One rank's rows of a dense design matrix, resident on its device.
 
@@ -116,7 +145,16 @@ class DenseShard:
         return self.features.numel() * self.features.element_size() + self.labels.numel() * self.labels.element_size()
 
     def eval(self, w: torch.Tensor, loss_type: int, mask: Optional[torch.Tensor] = None,
-             need_grad: bool = True):
+             need_grad: bool = True, sample_rows=False):
+        """``sample_rows`` (with a mask): run both data passes over the
+        compacted list of the sampled rows, so that only they are read.
+        ``True``, or the sampling fraction, which sizes the plan. The list
+        passes run on the raw features, also when a packed copy exists."""
+        if sample_rows and mask is not None:
+            return ops.dense_eval_rows(
+                self.features, self.labels, w, loss_type, mask, need_grad,
+                self.sample_weight,
+                expected_rows=_expected_rows(sample_rows, self.n))
         pk = self._packed_gpu()
         if pk is not None:
             return ops.dense_eval_packed(pk, self.labels, w, loss_type, mask,
@@ -406,7 +444,20 @@ class InterceptShard:
         return torch.cat([g, lc3[2:3].to(g.dtype)]), loss_count
 
     def eval(self, w: torch.Tensor, loss_type: int,
-             mask: Optional[torch.Tensor] = None, need_grad: bool = True):
+             mask: Optional[torch.Tensor] = None, need_grad: bool = True,
+             sample_rows=False):
+        if sample_rows and mask is not None:
+            # compact margins + b, sum of the compact multiplier, gradient
+            # over the list: the inner shard's sampled rows only
+            check_sample_rows(self)
+            d = self.inner.d
+            if w.numel() != d + 1:
+                raise ValueError(f"expected [w; b] of length {d + 1}, got {w.numel()}")
+            return ops.dense_eval_rows(
+                self.inner.features, self.labels, w[:d], loss_type, mask,
+                need_grad, self.sample_weight,
+                expected_rows=_expected_rows(sample_rows, self.n),
+                bias_src=w, bias_idx=d)
         grad, loss_count = self.eval_from_margins(self.margins(w), loss_type,
                                                   mask, need_grad)
         if grad is not None and grad.dtype != w.dtype:

@@ -19,6 +19,7 @@ from typing import Optional, Tuple
 import torch
 
 from .. import ops
+from ..data import check_sample_rows
 from ..ops import multiclass as mc
 
 
@@ -33,6 +34,7 @@ class Gradient:
         w: torch.Tensor,
         mask: Optional[torch.Tensor] = None,
         need_grad: bool = True,
+        sample_rows=False,
     ) -> Tuple[torch.Tensor, torch.Tensor]:
         """Return (grad_sum [d], loss_count float64 [2]) over the local shard.
 
@@ -41,8 +43,14 @@ class Gradient:
         all-reduced count happens in the optimizer, matching
         ``AGD.scala:206-207``. With ``need_grad=False`` only the loss side is
         computed (one data pass instead of two — used by the simple
-        backtracking test, which needs f_x but not g_x).
+        backtracking test, which needs f_x but not g_x). ``sample_rows``
+        (with a mask) is passed to the shard: both data passes then read the
+        sampled rows only (``DenseShard.eval``).
         """
+        if sample_rows and mask is not None:
+            check_sample_rows(shard, self)
+            return shard.eval(w, self.LOSS_TYPE, mask, need_grad,
+                              sample_rows=sample_rows)
         return shard.eval(w, self.LOSS_TYPE, mask, need_grad)
 
     def margins(self, shard, v: torch.Tensor) -> torch.Tensor:
@@ -141,7 +149,9 @@ class MultinomialLogisticGradient(Gradient):
                 "MultinomialLogisticGradient needs a bias per class, which "
                 "is not supported")
 
-    def eval(self, shard, w, mask=None, need_grad=True):
+    def eval(self, shard, w, mask=None, need_grad=True, sample_rows=False):
+        if sample_rows:
+            check_sample_rows(shard, self)  # raises: binary losses only
         return self.eval_from_margins(shard, self.margins(shard, w), mask,
                                       need_grad)
 

@@ -248,7 +248,11 @@ class MultiTaskGradient(Gradient):
                         want_f64=False)
         return g, lc
 
-    def eval(self, shard, w, mask=None, need_grad=True):
+    def eval(self, shard, w, mask=None, need_grad=True, sample_rows=False):
+        if sample_rows:
+            from ..data import check_sample_rows
+
+            check_sample_rows(shard, self)  # raises: binary losses only
         return self.eval_from_margins(shard, self.margins(shard, w), mask,
                                       need_grad)
 

@@ -667,8 +667,12 @@ class _SGDTrainer:
         feature_scaling: Union[bool, str] = False,
         intercept: bool = False,
         initial_intercept: float = 0.0,
+        sample_rows: bool = False,
     ) -> LinearModel:
-        """``feature_scaling``: ``False`` | ``True`` | ``"inplace"``, as in
+        """``sample_rows``: with ``mini_batch_fraction < 1`` on a resident
+        dense shard, run both data passes over the sampled rows only
+        (:func:`~sparkagd_amd.optimizer.run_mini_batch`).
+        ``feature_scaling``: ``False`` | ``True`` | ``"inplace"``, as in
         the AGD trainers (column standardisation before optimising; ``True``
         holds a scaled copy of the features during training; the regulariser
         acts on the scaled-space weights; returned weights and
@@ -689,7 +693,7 @@ class _SGDTrainer:
         opt = (GradientDescent(cls.GRADIENT_CLS(), updater, comm)
                .setStepSize(step_size).setNumIterations(num_iterations)
                .setRegParam(reg_param).setMiniBatchFraction(mini_batch_fraction)
-               .setStepSchedule(step_schedule))
+               .setStepSchedule(step_schedule).setSampleRows(sample_rows))
         if initial_weights is None:
             wdtype = torch.float64 if data.device.type == "cpu" else torch.float32
             initial_weights = torch.zeros(data.d, device=data.device, dtype=wdtype)

@@ -89,6 +89,30 @@ def dense_eval(
                                 need_grad, sample_weight)
 
 
+def dense_eval_rows(
+    features: torch.Tensor,
+    labels: torch.Tensor,
+    w: torch.Tensor,
+    loss_type: int,
+    mask: torch.Tensor,
+    need_grad: bool = True,
+    sample_weight: Optional[torch.Tensor] = None,
+    n_slabs: Optional[int] = None,
+    n_rb: Optional[int] = None,
+    **kw,
+):
+    """``dense_eval`` under a mini-batch mask, reading the sampled rows only:
+    on the GPU both data passes run over the compacted row list
+    (``hiplib.dense_eval_rows``, which documents the keywords); elsewhere
+    plain torch on ``features[rows]``."""
+    if _use_hip(features):
+        return _get_hip().dense_eval_rows(features, labels, w, loss_type, mask,
+                                          need_grad, sample_weight, n_slabs,
+                                          n_rb, **kw)
+    return reference.dense_eval_rows(features, labels, w, loss_type, mask,
+                                     need_grad, sample_weight, **kw)
+
+
 def csr_eval(
     rowptr: torch.Tensor,
     col: torch.Tensor,

@@ -190,6 +190,19 @@ def load() -> ctypes.CDLL:
     lib.agd_prox_tasks_free.restype = I
     lib.agd_prox_tasks_free.argtypes = [I, P, P, D, P, P, I, P, P, LL, LL, I,
                                         P, P]
+    # row-sampled mini-batch passes (csrc/agd_rows.hip)
+    lib.agd_compact_ws_ints.restype = LL
+    lib.agd_compact_ws_ints.argtypes = [LL]
+    lib.agd_compact_rows.restype = I
+    lib.agd_compact_rows.argtypes = [P, LL, P, P, P, P]
+    lib.agd_rows_margin_slabs.restype = I
+    lib.agd_rows_margin_slabs.argtypes = [LL, LL, LL, I]
+    lib.agd_rows_rowblocks.restype = LL
+    lib.agd_rows_rowblocks.argtypes = [LL, LL, I]
+    lib.agd_dense_eval_rows.restype = I
+    lib.agd_dense_eval_rows.argtypes = [P, I, P, P, P, P, LL, LL, LL, P, P, P,
+                                        P, P, P, P, P, LL, I, I, I, I, P, LL,
+                                        P, P]
 
     _lib = lib
     return lib
@@ -426,6 +439,121 @@ def dense_grad_from_mult(features: torch.Tensor, mult: torch.Tensor) -> torch.Te
     )
     _check(rc)
     return grad
+
+
+# --- row-sampled mini-batch passes (csrc/agd_rows.hip) ---------------------
+
+def _aligned_mask(mask: torch.Tensor, device) -> torch.Tensor:
+    """uint8 mask on the device whose base the 16-byte loads can take."""
+    mask = _prep_mask(mask, device)
+    if mask.data_ptr() % 16:
+        mask = mask.clone()
+    return mask
+
+
+def compact_rows(mask: torch.Tensor):
+    """(rows int32 [n], count int32 [1]) of a uint8 mask on the GPU: the
+    first ``count[0]`` entries of ``rows`` are the indices of the non-zero
+    mask bytes, ascending. The count stays on the device."""
+    lib = load()
+    n = mask.numel()
+    dev = mask.device
+    rows = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return rows, count
+    mask = _aligned_mask(mask, dev)
+    scan = torch.empty(int(lib.agd_compact_ws_ints(n)), dtype=torch.int32,
+                       device=dev)
+    _check(lib.agd_compact_rows(_ptr(mask), n, _ptr(rows), _ptr(count),
+                                _ptr(scan), _stream(mask)))
+    return rows, count
+
+
+def dense_eval_rows(
+    features: torch.Tensor,
+    labels: torch.Tensor,
+    w: torch.Tensor,
+    loss_type: int,
+    mask: torch.Tensor,
+    need_grad: bool = True,
+    sample_weight: Optional[torch.Tensor] = None,
+    n_slabs: Optional[int] = None,
+    n_rb: Optional[int] = None,
+    *,
+    expected_rows: Optional[int] = None,
+    bias_src: Optional[torch.Tensor] = None,
+    bias_idx: int = 0,
+    return_state: bool = False,
+):
+    """``dense_eval`` under ``mask`` with both data passes over the compacted
+    list of the rows with ``mask != 0``: only those rows are read.
+
+    ``expected_rows`` is the list length the slabs, row blocks and grids are
+    planned for (default: all rows); any actual length is served.
+    ``n_slabs`` / ``n_rb`` override the plan. With ``bias_src`` the margins
+    get ``+ bias_src[bias_idx]`` (read on the device) and the gradient has
+    ``d + 1`` entries, the sum of the multiplier last. ``return_state=True``
+    appends ``(rows, count, mult)``: the list, its device-side length and the
+    compact multiplier (entry i belongs to row ``rows[i]``)."""
+    n, d = features.shape
+    if mask is None or mask.numel() != n:
+        raise ValueError("dense_eval_rows needs a mask of one byte per row")
+    if n == 0:
+        grad, lc = _empty_shard_eval(features, need_grad)
+        if grad is not None and bias_src is not None:
+            grad = torch.zeros(d + 1, dtype=grad.dtype, device=grad.device)
+        return (grad, lc, None) if return_state else (grad, lc)
+    lib = load()
+    assert features.is_cuda and features.is_contiguous() and features.ndim == 2
+    a_dtype = _DTYPE_CODE[features.dtype]
+    acc = _ACC_DTYPE[features.dtype]
+    if w.dtype != acc:
+        raise TypeError(f"weights dtype {w.dtype} must be {acc} for {features.dtype} features")
+    dev = features.device
+    w = w.contiguous()
+    if w.data_ptr() % 16:  # a view into [w; b] may start anywhere
+        w = w.clone()
+    labels = labels.contiguous()
+    if labels.dtype != torch.float32:
+        labels = labels.to(torch.float32)
+    mask = _aligned_mask(mask, dev)
+    sw = _prep_weights(sample_weight, dev)
+    if bias_src is not None:
+        bias_src = _bias_src(bias_src, bias_idx, w)
+    expected = n if expected_rows is None else max(1, min(n, int(expected_rows)))
+    if n_slabs is None:
+        n_slabs = int(lib.agd_rows_margin_slabs(expected, n, d, a_dtype))
+    if n_rb is None:
+        n_rb = int(lib.agd_rows_rowblocks(expected, d, a_dtype))
+
+    out3 = torch.zeros(3, dtype=torch.float64, device=dev)
+    rows = torch.empty(n, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    scan = torch.empty(int(lib.agd_compact_ws_ints(n)), dtype=torch.int32,
+                       device=dev)
+    margins = torch.empty(n_slabs * n, dtype=acc, device=dev)
+    mult = torch.empty(n, dtype=acc, device=dev)
+    grad = gw = part = None
+    if need_grad:
+        grad = torch.empty(d + (bias_src is not None), dtype=acc, device=dev)
+        gw = grad[:d]
+        part = torch.empty(n_rb * d, dtype=acc, device=dev) if n_rb > 1 else None
+    rc = lib.agd_dense_eval_rows(
+        _ptr(features), a_dtype, _ptr(labels), _ptr(mask), _ptr(sw), _ptr(w),
+        n, d, expected, _ptr(gw), _ptr(out3), _ptr(rows), _ptr(count),
+        _ptr(scan), _ptr(margins), _ptr(mult), _ptr(part), n_rb, loss_type,
+        n_slabs, 1 if need_grad else 0,
+        int(os.environ.get("SPARKAGD_NT_LOADS", "1")), _ptr(bias_src),
+        bias_idx, _ptr(_red_ws(dev)), _stream(features),
+    )
+    _check(rc)
+    if need_grad and bias_src is not None:
+        grad[d:] = out3[2:3].to(acc)
+    loss_count = out3[:2]
+    if return_state:
+        return grad, loss_count, (rows, count, mult)
+    return grad, loss_count
 
 
 # --- 12-bit packed bf16 shard (one-time passes + packed stream) -----------

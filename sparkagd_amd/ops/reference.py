@@ -124,6 +124,47 @@ def dense_eval(
     return grad_sum, loss_count
 
 
+def dense_eval_rows(
+    features: torch.Tensor,
+    labels: torch.Tensor,
+    w: torch.Tensor,
+    loss_type: int,
+    mask: torch.Tensor,
+    need_grad: bool = True,
+    sample_weight: Optional[torch.Tensor] = None,
+    *,
+    expected_rows: Optional[int] = None,
+    bias_src: Optional[torch.Tensor] = None,
+    bias_idx: int = 0,
+    return_state: bool = False,
+):
+    """``dense_eval`` under ``mask`` on the gathered block ``features[rows]``
+    (``expected_rows`` only plans the GPU passes). With ``bias_src`` the
+    margins get ``+ bias_src[bias_idx]`` and the gradient ends with the sum
+    of the multiplier."""
+    rows = torch.nonzero(mask.reshape(-1) != 0).reshape(-1)
+    acc = dense_margins(features[:0], w).dtype
+    z = dense_margins(features[rows], w)
+    if bias_src is not None:
+        z = z + bias_src[bias_idx].to(z.dtype)
+    sw = None if sample_weight is None else sample_weight[rows]
+    mult, loss = _multiplier_and_loss(z, labels[rows], loss_type)
+    mult, loss, count = _apply_mask_weight(mult, loss, None, sw, rows.numel(),
+                                           features.device)
+    loss_count = torch.stack([loss.to(torch.float64).sum(), count])
+    grad = None
+    if need_grad:
+        grad = features[rows].to(acc).T @ mult.to(acc)
+        if bias_src is not None:
+            grad = torch.cat([grad, mult.to(acc).sum().reshape(1)])
+        grad = grad.to(w.dtype)
+    if return_state:
+        count_t = torch.tensor([rows.numel()], dtype=torch.int32,
+                               device=features.device)
+        return grad, loss_count, (rows.to(torch.int32), count_t, mult)
+    return grad, loss_count
+
+
 def csr_eval(
     rowptr: torch.Tensor,
     col: torch.Tensor,

@@ -29,6 +29,7 @@ import torch
 
 from . import ops
 from .config import AGDConfig
+from .data import check_sample_rows
 from .models.gradient import Gradient
 from .models.updater import SimpleUpdater, SquaredL2Updater, Updater
 from .parallel.comm import Communicator
@@ -582,6 +583,7 @@ def run_mini_batch(
     seed: int = 42,
     metrics=None,
     step_schedule: str = "sqrt",
+    sample_rows: bool = False,
 ) -> Tuple[torch.Tensor, List[float]]:
     """Mini-batch (S)GD — the golden-baseline optimizer.
 
@@ -593,7 +595,14 @@ def run_mini_batch(
     iteration number so the internal step decays as step_size/sqrt(i).
 
     On GPU the sampling is a seeded per-shard mask pushed into the gradient
-    kernels (masked rows contribute neither loss nor gradient).
+    kernels (masked rows contribute neither loss nor gradient). By default
+    the margins pass still streams the whole shard and only the gradient pass
+    skips the masked rows. ``sample_rows=True`` (off by default; a resident
+    dense shard, with or without an intercept; binary losses) compacts the
+    mask into a row list on the device and runs both passes over it, so a
+    step reads about 2f of the shard. It draws the same batches and differs
+    from the default only in summation order; ``mini_batch_fraction == 1.0``
+    ignores it.
 
     ``step_schedule``: 'sqrt' is MLlib's step_size/sqrt(i) (the default and
     the parity mode); 'constant' uses step_size; 'linear' is the
@@ -612,6 +621,9 @@ def run_mini_batch(
     device = w.device
     n_local = data.n
     use_mask = mini_batch_fraction < 1.0
+    sample_rows = bool(sample_rows) and use_mask
+    if sample_rows:
+        check_sample_rows(data, gradient)
 
     for i in range(1, num_iterations + 1):
         mask = None
@@ -621,7 +633,11 @@ def run_mini_batch(
             mask = (
                 torch.rand(n_local, generator=gen, device=device) < mini_batch_fraction
             ).to(torch.uint8)
-        grad_sum, loss_count = gradient.eval(data, w, mask)
+        if sample_rows:
+            grad_sum, loss_count = gradient.eval(
+                data, w, mask, sample_rows=mini_batch_fraction)
+        else:
+            grad_sum, loss_count = gradient.eval(data, w, mask)
         comm.allreduce_eval_(grad_sum, loss_count)
         lc = loss_count.to("cpu")
         loss_sum, batch_size = float(lc[0]), float(lc[1])
@@ -759,6 +775,7 @@ class GradientDescent(Optimizer):
         self.reg_param = 0.0
         self.mini_batch_fraction = 1.0
         self.step_schedule = "sqrt"
+        self.sample_rows = False
         self.seed = 42
         self.loss_history: List[float] = []
 
@@ -778,6 +795,12 @@ class GradientDescent(Optimizer):
         self.mini_batch_fraction = fraction
         return self
 
+    def setSampleRows(self, sample_rows: bool) -> "GradientDescent":
+        """Run the mini-batch passes over the sampled rows only
+        (:func:`run_mini_batch`'s ``sample_rows``)."""
+        self.sample_rows = bool(sample_rows)
+        return self
+
     def setStepSchedule(self, schedule: str) -> "GradientDescent":
         self.step_schedule = schedule
         return self
@@ -795,6 +818,6 @@ class GradientDescent(Optimizer):
             data, self.gradient, self.updater, self.step_size,
             self.num_iterations, self.reg_param, self.mini_batch_fraction,
             initial_weights, comm=self.comm, seed=self.seed,
-            step_schedule=self.step_schedule,
+            step_schedule=self.step_schedule, sample_rows=self.sample_rows,
         )
         return weights
